@@ -52,14 +52,9 @@ HIPFLAGS   := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off \
 CFLAGS_O   := -O2 -std=gnu11 -fPIC -ffp-contract=off -Wall -Wno-unused-function -Wno-unused-value -Wno-unused-result
 
 CTEST      := tests/c/_build/backend_ops
-# the reference-side adapter (integration/) compiled against the reference's
-# own headers, where they lie; skipped when the tree is absent (GPU box)
+# where the reference project's tree lies; the test programs that need it are
+# built by oracle/ref.mk into oracle/_ref/ (make adapter)
 REFERENCE  ?= /root/reference
-ADAPTER    := tests/c/_build/adapter_ops
-# the reference's own PDF unit tests (tests/pdf_{reader,writer}_test.c, compiled
-# where they lie) linked against integration/pdf_hip.c instead of MuPDF
-REF_PDF_TESTS := tests/c/_build/ref_pdf_reader_test tests/c/_build/ref_pdf_writer_test \
-                 tests/c/_build/ref_jbig2_decode_test
 
 LIBM_CHECK := tests/c/_build/libm_check
 SANITIZE   := tests/c/_build/sanitize
@@ -67,13 +62,12 @@ LLVMCC     := /opt/rocm/lib/llvm/bin/clang
 SANFLAGS   := -fsanitize=address,undefined -fno-sanitize-recover=undefined \
               -fno-omit-frame-pointer -g -O1
 
-.PHONY: all lib oracle ctest adapter sanitize libm_check jdec_emul j2k_emul clean
+.PHONY: all lib oracle ctest sanitize libm_check jdec_emul j2k_emul clean
 all: lib oracle ctest libm_check jdec_emul j2k_emul
 
 lib: $(LIB)
 oracle: $(ORACLE_LIB)
 ctest: $(CTEST)
-adapter: $(ADAPTER) $(REF_PDF_TESTS)
 
 $(OBJDIR)/%.hip.o: $(CSRC)/%.hip $(HDRS)
 	@mkdir -p $(OBJDIR)
@@ -102,28 +96,7 @@ $(CTEST): tests/c/backend_ops.c tests/c/pages.h include/unpaper_hip.h oracle/ora
 	  -L$(PKG)/lib -L oracle/_build -lunpaper_hip -loracle -lm \
 	  -Wl,-rpath,'$$ORIGIN/../../../$(PKG)/lib' -Wl,-rpath,'$$ORIGIN/../../../oracle/_build'
 
-$(ADAPTER): tests/c/adapter_main.c tests/c/pages.h integration/backend_hip.c integration/backend_hip.h \
-            integration/hip_frame.h include/unpaper_hip.h oracle/oracle.h $(LIB) $(ORACLE_LIB)
-	@test -f $(REFERENCE)/imageprocess/image.h || { echo "adapter: no reference headers under $(REFERENCE)"; exit 1; }
-	@mkdir -p tests/c/_build
-	$(CC) -O2 -std=gnu11 -Wall -Wno-unused-variable -I$(REFERENCE) -Iinclude -Iintegration \
-	  tests/c/adapter_main.c integration/backend_hip.c -o $@ \
-	  -L$(PKG)/lib -L oracle/_build -lunpaper_hip -loracle -lm \
-	  -Wl,-rpath,'$$ORIGIN/../../../$(PKG)/lib' -Wl,-rpath,'$$ORIGIN/../../../oracle/_build'
-
-tests/c/_build/ref_pdf_%_test: integration/pdf_hip.c include/unpaper_hip.h $(LIB)
-	@test -f $(REFERENCE)/tests/pdf_$*_test.c || { echo "ref pdf tests: no reference tree under $(REFERENCE)"; exit 1; }
-	@mkdir -p tests/c/_build
-	$(CC) -O2 -std=gnu11 -Wall -Wno-unused-variable -Wno-unused-function -I$(REFERENCE) -Iinclude \
-	  $(REFERENCE)/tests/pdf_$*_test.c integration/pdf_hip.c -o $@ \
-	  -L$(PKG)/lib -lunpaper_hip -lm -Wl,-rpath,'$$ORIGIN/../../../$(PKG)/lib'
-
-tests/c/_build/ref_jbig2_decode_test: integration/jbig2_hip.c integration/pdf_hip.c include/unpaper_hip.h $(LIB)
-	@test -f $(REFERENCE)/tests/jbig2_decode_test.c || { echo "ref jbig2 test: no reference tree under $(REFERENCE)"; exit 1; }
-	@mkdir -p tests/c/_build
-	$(CC) -O2 -std=gnu11 -Wall -Wno-unused-variable -Wno-unused-function -DUNPAPER_WITH_JBIG2 -DUNPAPER_WITH_PDF \
-	  -I$(REFERENCE) -Iinclude $(REFERENCE)/tests/jbig2_decode_test.c integration/jbig2_hip.c integration/pdf_hip.c \
-	  -o $@ -L$(PKG)/lib -lunpaper_hip -lm -Wl,-rpath,'$$ORIGIN/../../../$(PKG)/lib'
+include oracle/ref.mk
 
 # glibc sinf/cosf/powf(x, 2) restatement (csrc/libm_glibc.h) against this
 # host's libm; plain g++, contraction off like the device build.
@@ -179,4 +152,4 @@ sanitize: $(SANITIZE)
 	ASAN_OPTIONS=detect_leaks=1 UBSAN_OPTIONS=print_stacktrace=1 $(SANITIZE) $(CURDIR)/tests/c/_build/san $(CURDIR)/tests/golden/reference
 
 clean:
-	rm -rf $(PKG)/build $(PKG)/build_diag $(PKG)/lib $(PKG)/lib_diag oracle/_build tests/c/_build
+	rm -rf $(PKG)/build $(PKG)/build_diag $(PKG)/lib $(PKG)/lib_diag oracle/_build oracle/_ref tests/c/_build

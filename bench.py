@@ -10,8 +10,25 @@ cubic rotation, mask centering, border scan), driven by the native runner
 `--streams` batches of `--batch` sheets in flight per device.  The pages are
 generated straight into HBM before the clock starts; `value` counts pages
 processed with inputs and outputs resident in HBM (figure 1 of BASELINE.md
-§3).  Figures 2 (+ H2D/D2H through pinned staging) and 3 (+ PNM write) are
-measured after it with the host-fed runner over the same pages.
+§3).
+
+A plain run (`--gpus 1 --steps N --warmup W`) does only that: it sets up,
+warms up, times the N steps, writes its outputs if `--dump-outputs DIR` is
+given and prints the result line (`metric`, `value`, `unit`, `ms_per_step`,
+...); `--stages` adds the per-stage event times of those same steps on
+stderr, at no further run.  Everything below that is measured or checked
+beside the headline figure runs only with `--full`: the oracle-hash check, the roofline probe,
+the CPU baseline, the C2 latency, figures 2 (+ H2D/D2H through pinned
+staging) and 3 (+ PNM write) with the host-fed runner over the same pages,
+and the C4 object.
+
+`--dump-outputs DIR` writes, after the timed steps, what the timed path left
+for its caller in its last step: the sheets of the shard's last chunk, which
+the batch that ran it still holds (chunks go to idle batches, so of the other
+chunks only a varying subset stays resident).  Of each of these sheets a
+fixed, seeded choice of rows is written as float32, DIR/sheets_gpu<d>.npy of
+shape (sheets, rows, width), so two builds run with the same arguments can
+be compared value for value (the inputs are the same synthetic pages).
 
 One step = one pass of the pipeline over every page of each device's shard.
 N>1, driver style (torch.distributed.run): one process per GPU, pages sharded
@@ -20,13 +37,14 @@ the max-over-ranks of the elapsed time.  N>1 without torchrun (`--gpus N`):
 one process, one runner thread per device (the reference's thread pool bound
 to devices), device d processing pages [d*P, (d+1)*P).
 
-After the timed region every resident output page with a committed oracle
-hash (tests/golden/bench_hashes.json, tests/golden/make_bench_hashes.py) is
-hashed and compared; a mismatch fails the run.  A library built with the
+With `--full`, after the timed region every resident output page with a
+committed oracle hash (tests/golden/bench_hashes.json,
+tests/golden/make_bench_hashes.py) is hashed and compared; a mismatch fails
+the run.  A library built with the
 timing diagnostics (make lib DIAG=1) or an UPHIP_DIAG_* variable is refused
 unless --tuning (the line then says "valid": false).
 
-Extra fields: `roofline` for the dominant kernel (the bicubic rotation),
+Extra fields of a `--full` line: `roofline` for the dominant kernel (the bicubic rotation),
 timed with the HIP events its batch records on its own stream around the
 launch; `cpu_baseline` = the oracle's restatement of the reference CPU path
 on the host share of cores (rank 0, N=1 only); `latency_c2` = one A4 page
@@ -91,6 +109,15 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run what the default line reports beside "
+                         "its headline figure: the oracle-hash check, the roofline probe, the "
+                         "CPU baseline, the C2 latency, the host-fed figures and C4 (each can "
+                         "be dropped again with its --no-* switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the sheets the timed path's last step left resident for its "
+                         "caller (the shard's last chunk; a fixed seeded choice of rows) as "
+                         "DIR/sheets_gpu<d>.npy, float32")
     ap.add_argument("--config", default="c3", choices=("c3", "c4", "jpeg", "jp2", "pdf"),
                     help="c3: BASELINE configs[2] (the metric); c4: configs[3], RGB24 600dpi "
                          "double-page sheets, layout double, bilinear, border wipe; jpeg: the "
@@ -235,6 +262,49 @@ def verify_resident(runner, devices, firsts, npages, bsz, hashes):
                     print("bench: page %s differs from the oracle (device %d batch %d sheet %d)"
                           % (g, devices[i], k, s), file=sys.stderr)
     return checked, bad
+
+
+DUMP_BYTES = 48 * 1000 * 1000           # float32 bytes of one --dump-outputs run, all GPUs
+DUMP_SEED = 0x5eed
+
+
+def dump_outputs(path, runner, firsts, gpu0, n_gpus, npages, bsz):
+    """Write the sheets of each shard's last chunk (the last job of the last
+    timed step, so the batch that ran it still holds them) as
+    path/sheets_gpu<d>.npy: float32, (sheets, rows, bytes per row), the rows
+    a seeded choice that depends on the arguments only.  firsts: the first
+    global page of each device's shard.  Returns what the result line says
+    about the files this process wrote (under torchrun each rank writes its
+    own file; the line is rank 0's)."""
+    os.makedirs(path, exist_ok=True)
+    first = (npages - 1) // bsz * bsz
+    n = npages - first
+    files = []
+    rows = None
+    for i in range(len(firsts)):
+        # a batch left idle since an earlier pass may hold the same chunk too:
+        # the same pages through the same code, so whichever comes first
+        slot = next((k for k in range(runner.streams)
+                     if runner.slot_chunk(i, k) == (first, n)), None)
+        if slot is None:
+            raise UnpaperHipError("dump: no batch of device %d holds the last chunk" % i)
+        b = runner.batch(i, slot)
+        out = None
+        for s in range(n):
+            page = b.output(s).payload()
+            if out is None:
+                h, w = page.shape
+                nrows = max(1, min(h, DUMP_BYTES // max(n_gpus, 1) // (n * w * 4)))
+                rows = np.sort(np.random.default_rng(DUMP_SEED).choice(h, nrows, replace=False))
+                out = np.empty((n, nrows, w), np.float32)
+            out[s] = page[rows]
+        name = "sheets_gpu%d.npy" % (gpu0 + i)
+        np.save(os.path.join(path, name), out)
+        files.append(name)
+    return {"dir": path, "files": files,
+            "pages": [[f + first, f + first + n] for f in firsts], "rows": int(len(rows)),
+            "dtype": "float32", "what": "output sheets of the shard's last chunk, resident "
+                                        "after the last timed step; rows chosen by a fixed seed"}
 
 
 def stage_totals(runner, ndev):
@@ -869,6 +939,8 @@ def main():
     ndev = L.uphip_device_count()
     npages = args.pages or (16 if args.config == "c4" else 1000)
     devices, firsts, n_gpus = shard_plan(d.world, d.rank, d.local_rank, args.gpus, ndev, npages)
+    if args.dump_outputs and args.config != "c3":
+        raise SystemExit("bench.py: --dump-outputs is for the default configuration (c3)")
     if args.config == "c4":
         line = run_c4(args, L, d, devices, firsts, n_gpus, version, valid)
         if d.rank == 0:
@@ -918,15 +990,20 @@ def main():
     nchunks = (npages + bsz - 1) // bsz
     nlaunch = nchunks * args.steps * len(devices)
 
+    dumped = None
+    if args.dump_outputs:
+        dumped = dump_outputs(args.dump_outputs, runner, firsts,
+                              d.rank if d.world > 1 else 0, n_gpus, npages, bsz)
+
     checked = bad = 0
-    if not args.no_verify:
+    if args.full and not args.no_verify:
         checked, bad = verify_resident(runner, devices, firsts, npages, bsz,
                                        load_hashes("bench_hashes.json", "pages"))
         checked, bad = int(d.sum(float(checked))), int(d.sum(float(bad)))
 
-    totals = stage_totals(runner, len(devices))
+    totals = stage_totals(runner, len(devices)) if args.full or args.stages else {}
     roofline = None
-    if ROOFLINE_STAGE in totals:
+    if args.full and ROOFLINE_STAGE in totals:
         # In the timed region `streams` batches share the GPU, so one launch's
         # event span is stretched by the kernels of the other streams; the
         # kernel's own duration comes from probe launches right after it: the
@@ -958,7 +1035,8 @@ def main():
                   file=sys.stderr)
     runner.close()
 
-    single = d.world == 1 and len(devices) == 1
+    # everything measured beside the headline figure: --full runs only
+    single = args.full and d.world == 1 and len(devices) == 1
     c4 = None
     if single and not args.no_c4:
         note("C3 done (%.0f pages/s); C4" % pages_per_s)
@@ -1023,10 +1101,13 @@ def main():
                                        if d.world > 1 else
                                        "one runner thread per device, pages sharded")
                        + ", no collective"},
-            "roofline": roofline, "cpu_baseline": cpu, "latency_c2": latency, "host_io": hio,
-            "c4": c4,
-            "verified": checked, "mismatches": bad, "library": version, "valid": valid,
+            "full": args.full, "library": version, "valid": valid,
         }
+        if dumped:
+            out["dumped"] = dumped
+        if args.full:
+            out.update({"roofline": roofline, "cpu_baseline": cpu, "latency_c2": latency,
+                        "host_io": hio, "c4": c4, "verified": checked, "mismatches": bad})
         print(json.dumps(out), flush=True)
     d.close()
     if bad:

@@ -8,7 +8,7 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EXE = os.path.join(ROOT, "tests", "c", "_build", "backend_ops")
-ADAPTER = os.path.join(ROOT, "tests", "c", "_build", "adapter_ops")
+ADAPTER = os.path.join(ROOT, "oracle", "_ref", "adapter_ops")
 REFERENCE_HEADERS = "/root/reference/imageprocess/image.h"
 
 
@@ -38,12 +38,14 @@ def test_c_caller_all_ops_match_oracle():
 
 def _adapter():
     """integration/backend_hip.c compiled against the reference's own headers
-    (make adapter); prebuilt here, where the reference tree is, and carried to
-    the GPU box with the tree."""
+    (make adapter, oracle/ref.mk) into oracle/_ref/: built here where the
+    reference's tree is, else the one build() made where it is and that was
+    carried over with oracle/_ref/.  A missing program is a failure."""
     if os.path.isfile(REFERENCE_HEADERS):
         subprocess.check_call(["make", "-s", "adapter"], cwd=ROOT)
     if not os.path.exists(ADAPTER):
-        pytest.fail("tests/c/_build/adapter_ops is not built (run build() where the reference is)")
+        pytest.fail("oracle/_ref/adapter_ops is not built: run build() where the reference's "
+                    "tree is and bring oracle/_ref/ along")
     return ADAPTER
 
 

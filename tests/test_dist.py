@@ -95,3 +95,56 @@ def test_product_library_has_no_diagnostics():
         blob = f.read()
     assert b"UPHIP_DIAG" not in blob
     assert b"UPHIP_DEBUG" not in blob
+
+
+def test_dump_outputs_is_a_fixed_sample_of_the_last_chunk(tmp_path):
+    """--dump-outputs: of the batch that holds the shard's last chunk (72
+    pages in 64-sheet batches: pages 64..71) a seeded choice of rows of every
+    sheet, float32, within the 64 MB the option may write, the same from run
+    to run."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    h, w = 3508, 2480
+
+    def sheet(page):
+        return np.random.default_rng(page).integers(0, 256, (h, w), dtype=np.uint8)
+
+    class Image:
+        def __init__(self, a):
+            self.a = a
+
+        def payload(self):
+            return self.a
+
+    class FakeBatch:
+        def __init__(self, first):
+            self.first = first
+
+        def output(self, s):
+            return Image(sheet(self.first + s))
+
+    class FakeRunner:
+        streams = 3
+        chunks = [(0, 64), (64, 8), None]
+
+        def slot_chunk(self, i, k):
+            return self.chunks[k]
+
+        def batch(self, i, k):
+            return FakeBatch(self.chunks[k][0])
+
+    info = bench.dump_outputs(str(tmp_path / "a"), FakeRunner(), [0], 0, 1, 72, 64)
+    assert info["files"] == ["sheets_gpu0.npy"] and info["pages"] == [[64, 72]]
+    got = np.load(tmp_path / "a" / "sheets_gpu0.npy")
+    assert got.dtype == np.float32 and got.shape == (8, info["rows"], w)
+    assert 1 < info["rows"] <= h and got.nbytes <= 64e6
+    rows = np.sort(np.random.default_rng(bench.DUMP_SEED).choice(h, info["rows"], replace=False))
+    for s in range(8):
+        assert np.array_equal(got[s], sheet(64 + s)[rows].astype(np.float32)), s
+    bench.dump_outputs(str(tmp_path / "b"), FakeRunner(), [0], 0, 1, 72, 64)
+    assert np.array_equal(got, np.load(tmp_path / "b" / "sheets_gpu0.npy"))
+    # all GPUs of a job share the budget; pages are numbered over the whole job
+    info2 = bench.dump_outputs(str(tmp_path / "c"), FakeRunner(), [72], 1, 2, 72, 64)
+    assert info2["files"] == ["sheets_gpu1.npy"] and info2["pages"] == [[136, 144]]
+    assert info2["rows"] <= info["rows"] // 2 + 1

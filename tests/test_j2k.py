@@ -39,6 +39,9 @@ FIXTURES = os.path.join(ROOT, "tests", "golden", "j2k")
 def _emul():
     from unpaper_hip.device import load_library
     load_library()  # the emulator links the library
+    if not os.path.exists(EMUL):
+        import subprocess
+        subprocess.check_call(["make", "-s", "j2k_emul"], cwd=ROOT)
     E = C.CDLL(EMUL)
     E.j2k_emulate.restype = C.c_int64
     E.j2k_emulate.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int64, C.c_void_p]

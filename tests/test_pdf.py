@@ -645,17 +645,21 @@ def test_runner_host_decoded_pdf_pages(hip, oracle, tmp_path):
 # the reference's own PDF unit tests (tests/pdf_reader_test.c,
 # tests/pdf_writer_test.c in the reference), compiled where they lie against
 # integration/pdf_hip.c -- the reference's reader / writer API on this
-# library instead of MuPDF (make adapter; built here, run here and on the box)
+# library instead of MuPDF (make adapter, oracle/ref.mk: built into oracle/_ref/
+# where the reference's tree is; a machine without it runs what was carried over)
 # ---------------------------------------------------------------------------
-REF_PDF = {k: os.path.join(ROOT, "tests", "c", "_build", "ref_pdf_%s_test" % k) for k in ("reader", "writer")}
-REF_PDF["jbig2"] = os.path.join(ROOT, "tests", "c", "_build", "ref_jbig2_decode_test")
+REF_PDF = {k: os.path.join(ROOT, "oracle", "_ref", "ref_pdf_%s_test" % k) for k in ("reader", "writer")}
+REF_PDF["jbig2"] = os.path.join(ROOT, "oracle", "_ref", "ref_jbig2_decode_test")
 
 
-def _ref_pdf_run(which, tmp_path):
+def _ref_pdf_run(which, tmp_path, required=False):
     import subprocess
     exe = REF_PDF[which]
     if not os.path.exists(exe):
         if not os.path.isdir("/root/reference/tests"):
+            if required:
+                pytest.fail("%s is not built: run build() where the reference's tree is and "
+                            "bring oracle/_ref/ along" % os.path.relpath(exe, ROOT))
             pytest.skip("reference tree absent and %s not prebuilt" % exe)
         subprocess.check_call(["make", "-s", os.path.relpath(exe, ROOT)], cwd=ROOT)
     # the tests find tests/pdf_samples beside $TEST_IMGSRC_DIR and a JPEG in it
@@ -688,7 +692,7 @@ def test_reference_pdf_reader_unit_tests_host(tmp_path):
 def test_reference_pdf_reader_unit_tests(hip, tmp_path):
     """All of pdf_reader_test.c, render tests included (image pages: the
     page's image decoded on the device, box-resampled to the page at 150 dpi)."""
-    r = _ref_pdf_run("reader", tmp_path)
+    r = _ref_pdf_run("reader", tmp_path, required=True)
     assert r.returncode == 0 and "All tests passed!" in r.stdout, r.stdout + r.stderr
     assert "FAILED" not in r.stdout and "SKIPPED" not in r.stdout
 

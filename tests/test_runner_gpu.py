@@ -43,7 +43,8 @@ def _bench(*extra, timeout=300):
     for k in list(env):
         if k.startswith("UPHIP_DIAG"):
             del env[k]
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu", "--no-host-io",
+    # --full for the oracle-hash check of the resident outputs, without its other legs
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu", "--no-host-io",
            "--no-latency", "--no-c4", "--probe", "0"] + list(extra)
     p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=timeout)
     assert p.returncode == 0, p.stderr[-3000:]
@@ -67,6 +68,62 @@ def test_bench_four_streams_rerun_before_wait():
     """4 batches of 64 over 256 pages, 3 passes enqueued before one wait."""
     out = _bench("--pages", "256", "--streams", "4", "--steps", "3", "--warmup", "0")
     assert out["verified"] >= 64 and out["mismatches"] == 0
+
+
+def test_bench_plain_run_and_dump(hip, tmp_path):
+    """A plain run (no --full) times the steps and prints the headline line
+    without the --full legs; --dump-outputs writes seeded rows of the sheets
+    the last timed step leaves resident.  72 pages in 64-sheet batches leave
+    pages 64..71: two runs dump the same values, and these equal the same
+    pages through one batch run directly, whose whole sheets equal the
+    oracle's hashes."""
+    import ctypes
+    sys.path.insert(0, ROOT)
+    import bench
+    from unpaper_hip.workloads import A4_H, A4_W
+    env = {k: v for k, v in os.environ.items() if not k.startswith("UPHIP_DIAG")}
+    dumps = []
+    for run in ("a", "b"):
+        dump = tmp_path / run
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--pages", "72",
+               "--streams", "2", "--steps", "2", "--warmup", "1", "--dump-outputs", str(dump)]
+        p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=120)
+        assert p.returncode == 0, p.stderr[-3000:]
+        line = json.loads(p.stdout.strip().splitlines()[-1])
+        assert line["full"] is False and line["steps"] == 2 and line["valid"] is True
+        assert line["unit"] == "pages/s" and line["ms_per_step"] > 0
+        # value and ms_per_step (rounded to 0.01 ms) describe the same timed steps
+        assert abs(line["value"] * line["ms_per_step"] * 1e-3 - 72) <= 0.01 * 72
+        for k in ("verified", "roofline", "cpu_baseline", "latency_c2", "host_io", "c4"):
+            assert k not in line
+        assert line["dumped"]["files"] == ["sheets_gpu0.npy"]
+        assert line["dumped"]["pages"] == [[64, 72]]
+        assert sorted(os.listdir(dump)) == ["sheets_gpu0.npy"]
+        dumps.append(np.load(dump / "sheets_gpu0.npy"))
+    got = dumps[0]
+    assert got.dtype == np.float32 and got.nbytes <= 64e6
+    assert got.shape[0] == 8 and got.shape[2] == A4_W and 1 < got.shape[1] <= A4_H
+    assert np.array_equal(got, dumps[1])
+
+    hashes = json.load(open(os.path.join(GOLDEN, "bench_hashes.json")))["pages"]
+    opts = A.Options()
+    hip.lib.uphip_options_init(ctypes.byref(opts))
+    pitch = (A4_W + 255) // 256 * 256
+    buf = DeviceBuffer(pitch * A4_H * 8)
+    b = Batch(opts, 8, A4_W, A4_H, A.FMT_GRAY8)
+    try:
+        assert hip.lib.uphip_synth_pages(buf.ptr, pitch, pitch * A4_H, A4_W, A4_H, 64, 8) == 0
+        b.run_device(8, buf.ptr, pitch, pitch * A4_H)
+        b.wait()
+        for s in range(8):
+            out = b.output(s).payload()
+            assert hashlib.sha256(out.tobytes()).hexdigest() == hashes[str(64 + s)], s
+            rows = np.sort(np.random.default_rng(bench.DUMP_SEED).choice(
+                out.shape[0], got.shape[1], replace=False))
+            assert np.array_equal(got[s], out[rows].astype(np.float32)), s
+    finally:
+        b.close()
+        buf.close()
 
 
 def _pages(n, first, w, h):

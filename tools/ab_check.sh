@@ -12,7 +12,7 @@ timeout -k 10 400 python3 -u -m pytest tests/test_pipeline_gpu.py tests/test_ops
 tail -1 gpurun_out/abc_tests.log
 for v in old new; do
   cp ab/$v.so unpaper-gpu_amd/lib/libunpaper_hip.so
-  timeout -k 10 120 python3 bench.py --no-cpu --no-host-io --no-latency --pages 256 --steps 1 --probe 5 \
+  timeout -k 10 120 python3 bench.py --full --no-cpu --no-host-io --no-latency --pages 256 --steps 1 --probe 5 \
     > gpurun_out/abc_probe_$v.json 2>&1 || { tail gpurun_out/abc_probe_$v.json; exit 1; }
   python3 -c "import json; d=json.loads(open('gpurun_out/abc_probe_$v.json').read().strip().splitlines()[-1]); print('$v isolated rotate ms', d['roofline']['avg_launch_ms'])"
 done

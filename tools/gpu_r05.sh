@@ -12,6 +12,6 @@ if [ -n "$K" ]; then
   tail -3 $o/gpu_tests.log
 fi
 if [ "${BENCH:-0}" = 1 ]; then
-  timeout -k 10 400 python3 bench.py ${BENCH_ARGS:-} > $o/bench.json 2> $o/bench.err || { tail -20 $o/bench.err; exit 1; }
+  timeout -k 10 400 python3 bench.py --full ${BENCH_ARGS:-} > $o/bench.json 2> $o/bench.err || { tail -20 $o/bench.err; exit 1; }
   tail -c 3000 $o/bench.json
 fi

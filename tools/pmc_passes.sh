@@ -11,7 +11,7 @@ n=0
 for C in "$@"; do
   n=$((n+1))
   timeout -s KILL 120 rocprofv3 --pmc $C --output-format csv -d gpurun_out/pmc_${tag}_$n -- \
-    python3 bench.py --no-cpu --no-host-io --no-latency --no-verify --pages 128 --steps 1 --warmup 0 \
+    python3 bench.py --full --no-cpu --no-host-io --no-latency --no-verify --pages 128 --steps 1 --warmup 0 \
     --streams 1 --probe 0 > gpurun_out/pmc_${tag}_$n.log 2>&1 || { tail -5 gpurun_out/pmc_${tag}_$n.log; exit 1; }
   python3 profiles/pmc_summary.py "$(dirname $(find gpurun_out/pmc_${tag}_$n -name '*counter_collection.csv' | head -1))" > gpurun_out/pmc_${tag}_$n.txt
   echo "pass $n: $C"; head -60 gpurun_out/pmc_${tag}_$n.txt

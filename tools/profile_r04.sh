@@ -12,7 +12,7 @@ out=gpurun_out/r04
 mkdir -p $out
 Q="--no-cpu --no-host-io --no-latency --no-verify --no-c4 --pages 128 --steps 1 --warmup 0 --streams 1 --probe 0"
 timeout -s KILL 240 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -- \
-  python3 bench.py --steps 5 --no-host-io --no-cpu --no-c4 > $out/trace.log 2>&1 || { tail -5 $out/trace.log; exit 1; }
+  python3 bench.py --full --steps 5 --no-host-io --no-cpu --no-c4 > $out/trace.log 2>&1 || { tail -5 $out/trace.log; exit 1; }
 echo "trace done"; tail -1 $out/trace.log | cut -c1-200
 timeout -s KILL 120 rocprofv3 --kernel-trace --stats --output-format csv -d $out/iso -- python3 bench.py $Q > $out/iso.log 2>&1 || { tail -5 $out/iso.log; exit 1; }
 python3 profiles/summarize.py $out/iso 2 > $out/kernel_stats_1stream.txt && head -45 $out/kernel_stats_1stream.txt

@@ -15,7 +15,7 @@ fi
 if [ "${BLACK:-0}" = 1 ]; then
   Q="--tuning --no-cpu --no-host-io --no-latency --no-verify --pages 64 --steps 1 --warmup 0 --streams 1 --probe 0"
   UNPAPER_HIP_LIB=unpaper-gpu_amd/lib_diag/libunpaper_hip.so UPHIP_DIAG_NOISE=16 timeout -k 10 300 \
-    python3 bench.py $Q > $o/black_diag.txt 2>&1 || { tail -5 $o/black_diag.txt; exit 1; }
+    python3 bench.py --full $Q > $o/black_diag.txt 2>&1 || { tail -5 $o/black_diag.txt; exit 1; }
   grep "uphip black" $o/black_diag.txt | sort | uniq -c | sort -rn | head -12
 fi
 for c in ${CFG:-}; do

@@ -9,7 +9,7 @@ cd "$GRAFT_REPO_ROOT" || exit 1
 mkdir -p gpurun_out
 for v in ${VARIANTS:-0 512 1536 2048 4096}; do
   UNPAPER_HIP_LIB=unpaper-gpu_amd/lib_diag/libunpaper_hip.so UPHIP_DIAG_DOUBLE=$v timeout -k 10 120 \
-    python3 bench.py --tuning --no-cpu --no-c4 --no-host-io --no-latency --no-verify --pages 256 \
+    python3 bench.py --full --tuning --no-cpu --no-c4 --no-host-io --no-latency --no-verify --pages 256 \
     --steps 1 --probe 5 > gpurun_out/rv$v.json 2> gpurun_out/rv$v.err || { tail -5 gpurun_out/rv$v.err; exit 1; }
   python3 -c "import json; d=json.loads(open('gpurun_out/rv$v.json').read().strip().splitlines()[-1]); print('variant $v rotate ms', d['roofline']['avg_launch_ms'])"
 done
