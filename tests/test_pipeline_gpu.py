@@ -507,7 +507,7 @@ def test_center_move_border_counts(hip, oracle):
 
 
 # ---------------------------------------------------------------------------
-# the two-launch GRAY8 bicubic rotation (kernels_blit.hip launch_rotate_mask)
+# the two-launch GRAY8 bicubic rotation (kernels_rotate.hip launch_rotate_mask)
 # ---------------------------------------------------------------------------
 def skewed_page(w, h, deg, seed):
     """White page, a block of 3x3-cell text lines rotated by `deg` degrees
@@ -579,7 +579,7 @@ def _blank_band(w, h, page, top, bottom):
 @pytest.mark.parametrize("align", ["center", "top", "bottom_right"])
 def test_chained_center_border_align(hip, oracle, margins, align):
     """The centring move, the border scan and the masked align move chained
-    (pipeline.hip chain_center_align, kernels_blit.hip k_move_chain_g16):
+    (pipeline.hip chain_center_align, kernels_move.hip k_move_chain_g16):
     the scan first counts only the rows within 320 of each edge; pages whose
     margin is wider (the top, the bottom or both blanked past 320 rows) make
     it count the middle rows and scan again.  Whole sheets against the

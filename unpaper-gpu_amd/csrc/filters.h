@@ -95,9 +95,6 @@ struct BlackGeom {
 bool black_geometry(int32_t W, int32_t H, const UphipBlackfilterParameters& p, uint8_t mask_max,
                     BlackGeom* g, BlackBar* bars, int max_bars);
 size_t black_scratch_bytes(const BlackGeom& g);
-void launch_blackfilter(const PlaneRef& img, const BlackGeom& g, const BlackBar* bars,
-                        void* scratch, int64_t scratch_stride, const int32_t* active,
-                        SheetCtl* ctl, int count, hipStream_t st);
 
 // ---- rotation detection (deskew.c:48-241) -------------------------------
 constexpr int kMaxAngles = 512;

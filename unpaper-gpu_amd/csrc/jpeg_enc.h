@@ -9,7 +9,7 @@
 // runs on the device, on the batch's stream right after its pipeline, and
 // only the finished file images cross PCIe:
 //
-//   A  k_jenc_count  per tile of 256 MCUs (8 rounds of 32 MCUs, 8 lanes per
+//   A  k_jenc_tile   <kEmit false> per tile of 256 MCUs (8 rounds of 32 MCUs, 8 lanes per
 //                    MCU): colour conversion + downsampling (jccolor.c,
 //                    jcsample.c), islow forward DCT (jfdctint.c) with a
 //                    uniform-block shortcut, quantisation by reciprocal
@@ -17,7 +17,7 @@
 //                    tile's bit count and its first / last DC per component
 //   B  k_jenc_scan   per image: tile bit offsets (+ the DC differences that
 //                    cross tiles), overflow check against the bit buffer
-//   C  k_jenc_emit   per tile again (DCT recomputed: cheaper than storing
+//   C  k_jenc_tile   <kEmit true> per tile again (DCT recomputed: cheaper than storing
 //                    2 B per coefficient): each lane ORs its codes into an
 //                    LDS window of the bit stream at its exact offset; whole
 //                    words go to HBM, a tile's first and last (shared) words

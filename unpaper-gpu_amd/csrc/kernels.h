@@ -60,17 +60,35 @@ struct RotateArgs {  // deskew (deskew.c:248-286)
 };
 
 // ---- launchers (kernels_blit.hip) ---------------------------------------
-void launch_fill(const PlaneRef& dst, const FillArgs* args, int count, int rows_hint,
-                 hipStream_t st);
-void launch_copy(const PlaneRef& src, const PlaneRef& dst, const CopyArgs* args, int count,
-                 int rows_hint, hipStream_t st);
-void launch_apply_masks(const PlaneRef& dst, const MaskArgs* args, int count, hipStream_t st);
-void launch_mirror(const PlaneRef& img, bool horizontal, bool vertical, int count,
-                   hipStream_t st);
-void launch_rotate90(const PlaneRef& src, const PlaneRef& dst, int direction, int count,
-                     hipStream_t st);
-void launch_stretch(const PlaneRef& src, const PlaneRef& dst, int interp, int count,
-                    hipStream_t st);
+// `thr` is the target frame's abs_black_threshold: where the target is 1 bit
+// per pixel, a written pixel is black when its gray value is below thr
+// (set_pixel, pixel.c:142-168).  Other target formats ignore it.
+// wipe_rectangle: args[s].r (already clipped) <- args[s].color; thr as above.
+void launch_fill_thr(const PlaneRef& dst, const FillArgs* args, int count, int rows_hint,
+                     uint8_t thr, hipStream_t st);
+// copy_rectangle: src's area args[s].a to (tx, ty) of dst; thr as above.
+void launch_copy_thr(const PlaneRef& src, const PlaneRef& dst, const CopyArgs* args, int count,
+                     int rows_hint, uint8_t thr, hipStream_t st);
+// apply_masks: pixels outside every mask <- args[s].color; thr as above.
+void launch_apply_masks_thr(const PlaneRef& dst, const MaskArgs* args, int count, uint8_t thr,
+                            hipStream_t st);
+// mirror, out of place (dst the size of src); thr as above.
+void launch_mirror_oop(const PlaneRef& src, const PlaneRef& dst, bool h, bool v, uint8_t thr,
+                       int count, hipStream_t st);
+// flip_rotate_90 (direction > 0: clockwise), dst W x H = src H x W; thr as above.
+void launch_rotate90_thr(const PlaneRef& src, const PlaneRef& dst, int direction, uint8_t thr,
+                         int count, hipStream_t st);
+// stretch_frame: dst's size from src's with `interp`; thr as above.
+void launch_stretch_thr(const PlaneRef& src, const PlaneRef& dst, int interp, uint8_t thr,
+                        int count, hipStream_t st);
+// shift: dst <- bg, src copied at (dx, dy); thr as above.
+void launch_shift(const PlaneRef& src, const PlaneRef& dst, int dx, int dy, const uint8_t bg[3],
+                  uint8_t thr, int count, hipStream_t st);
+// Flip `cur` of every sheet whose args[s].active (int at byte offset) is set.
+void launch_flip_if_active(SheetCtl* ctl, const int32_t* active, int64_t stride_bytes,
+                           int count, hipStream_t st);
+
+// ---- launchers (kernels_move.hip) ---------------------------------------
 void launch_move_rect(const PlaneRef& src, const PlaneRef& dst, const MoveArgs* args,
                       int count, hipStream_t st);
 // Work folded into a gray move (k_move_rect_g16), each optional:
@@ -104,6 +122,8 @@ bool launch_move_chain(const PlaneRef& src, const PlaneRef& dst, const MoveArgs*
 // Returns false (nothing launched) unless the plane is GRAY8.
 bool launch_move_rect_fused(const PlaneRef& src, const PlaneRef& dst, const MoveArgs* args,
                             const MoveExtra& x, int count, hipStream_t st);
+
+// ---- launchers (kernels_rotate.hip) -------------------------------------
 // max_abs_angle bounds |rotation| of every active sheet (sizes the staged
 // source window; tiles whose window does not fit take a slower exact path).
 // colsum (optional, zeroed by the caller for the rotated sheets): the
@@ -122,8 +142,5 @@ struct LinWindow {
 bool launch_rotate_linear(const PlaneRef& src, const PlaneRef& dst, const RotateArgs* args,
                           int nmask, int64_t mstride, const int32_t* indep, int count,
                           hipStream_t st, float max_abs_angle);
-// Flip `cur` of every sheet whose args[s].active (int at byte offset) is set.
-void launch_flip_if_active(SheetCtl* ctl, const int32_t* active, int64_t stride_bytes,
-                           int count, hipStream_t st);
 
 }  // namespace uph

@@ -711,9 +711,6 @@ __device__ __forceinline__ void check_cursor(const int32_t (&cs)[5], int32_t c, 
 // cursor's line from the cursor, then the following lines from their first
 // position -- as many windows as each needs, so a long line is read 2048
 // positions a trip instead of 512 (a C3 band column is 3508 long).
-#ifndef UPH_BLACK_PLAN
-#define UPH_BLACK_PLAN 1
-#endif
 // positions a lane reads on one side of a line per scan trip: UPH_BLACK_SPAN
 // windows of 64 (32 lanes a side: 4096 positions a trip at 2)
 #ifndef UPH_BLACK_SPAN
@@ -804,16 +801,12 @@ __device__ __forceinline__ int32_t check_eval_plan(const Sheet& S, const Win (&w
   return c;
 }
 
-// One planned scan trip, out of line: it is taken for long lines only, and
-// inlined it costs every frame of the replay SGPR spills.
-#ifndef UPH_BLACK_PLAN_NOINLINE
-#define UPH_BLACK_PLAN_NOINLINE 0
-#endif
-#if UPH_BLACK_PLAN_NOINLINE
-__device__ __attribute__((noinline))
-#else
+// One planned scan trip, inlined into check_scan<true>.  It is taken for long
+// lines only, and its SGPRs would cost every frame of the replay spills; the
+// replay is templated on LONG instead (chosen by sheet size), so sheets that
+// cannot have a long line run an instantiation without it.  An out-of-line
+// call was the alternative and did not ship.
 __device__ __forceinline__
-#endif
 int32_t check_trip_plan(const Sheet& S, const Frame& f, const int32_t (&cs)[5], int dc, int32_t sub,
                         int32_t pc, int32_t* resume, int32_t* next) {
   const ChkPlan pl = check_plan(f, cs, dc, pc);
@@ -842,7 +835,7 @@ __device__ __forceinline__ int32_t check_scan(const Sheet& S, const Frame& f,
     bool longl = pick4(f.dist, dc) - pc + 1 > 64 * kChkWin;
 #pragma unroll
     for (int d = 0; d < 4; d++) longl |= d > dc && f.dist[d] > 64 * kChkWin;
-    if (LONG && UPH_BLACK_PLAN && longl) {
+    if (LONG && longl) {
       r = check_trip_plan(S, f, cs, dc, sub, pc, resume, &nx);
     } else {
       Win w;

@@ -295,7 +295,7 @@ __device__ __forceinline__ bool band_range(const RotScratch& R, int tbase, int n
   return *bw <= band_cap && lo <= hi;
 }
 
-// ---- k_rot_band: slice sums of every angle x kDepth steps -----------------
+// ---- k_rot_band_g: slice sums of every angle x kDepth steps -----------------
 // Along a slice a line's column changes only where (int)X steps, so it is a
 // few vertical runs (1 + 128*|m| at most).  The slice's band is staged as
 // per-column prefix sums over its rows (16-bit: 128 * 255 fits), and every

@@ -129,9 +129,6 @@ __global__ void __launch_bounds__(256) k_gray_cells(PlaneRef img, GrayGeom g, ui
 // the image the grayfilter leaves; k_gray_wipe adds what its wipes change), so
 // that scan needs no pass of its own.  kGrayStrips strips per block keep the
 // atomics at W per kGrayStrips * ch rows.
-#ifndef UPH_GRAY_ROWS
-#define UPH_GRAY_ROWS 1  // k_gray_tiles_rows (0: a thread per tile reading its cells)
-#endif
 constexpr int kGrayStripMaxW = 16384;
 constexpr int kGrayStrips = 8;
 constexpr int kGrayMaxCh = 255;
@@ -463,7 +460,7 @@ static bool launch_gray_t(const PlaneRef& img, const GrayGeom& g, uint8_t* scr, 
   }
   const int32_t ntiles = g.ntx * g.nty;
   const size_t rows_lds = 2 * sizeof(uint32_t) * (size_t)g.th * g.ncx;
-  if (UPH_GRAY_ROWS && rows_lds <= (size_t)kGrayRowLds)
+  if (rows_lds <= (size_t)kGrayRowLds)
     hipLaunchKernelGGL(k_gray_tiles_rows, dim3(g.nty, count), dim3(256), rows_lds, st, g, scr, ss, active);
   else
     hipLaunchKernelGGL(k_gray_tiles, dim3((ntiles + 255) / 256, count), dim3(256), 0, st, g, scr, ss,
@@ -1224,7 +1221,7 @@ static int group_threads(int32_t W, int32_t H) { return (int64_t)W * H > (16 << 
 size_t noise_scratch_bytes(const NoiseGeom& g) {
   // lists + a global sort buffer for the rare > 8192-trigger sequential case;
   // the GRAY8 dark bit-plane shares the sort buffer's space (it is read by
-  // k_noise_classify only, before k_noise_resolve may sort)
+  // k_noise_classify only, before k_noise_group may sort)
   // (and k_noise_group's keys / roots / last, 3 x its LDS cap words)
   size_t sort = 4 * pow2_at_least((size_t)g.capacity);
   const size_t cap3 = 12 * (size_t)kCapPerThread * (size_t)group_threads(g.W, g.H);
@@ -2437,17 +2434,6 @@ __device__ void noise_raster_replay(uint32_t* keys, int n, int p2, const NoiseGe
   }
 }
 
-// UPH_NOISE_CHECK (tuning builds): index checks in k_noise_group that print
-// and skip the access instead of faulting; NCHK(...) is `true` otherwise.
-#ifdef UPH_NOISE_CHECK
-__device__ __forceinline__ bool nchk(bool ok, int tag, long long idx, unsigned n) {
-  if (!ok) printf("uphip noise check: sheet %d tag %d idx %lld n %u\n", (int)blockIdx.x, tag, idx, n);
-  return ok;
-}
-#define NCHK(ok, tag, idx) nchk((ok), (tag), (long long)(idx), n)
-#else
-#define NCHK(ok, tag, idx) true
-#endif
 // k_noise_group's ordering and linking for one sheet of n (> 0) triggers;
 // BIG (n > kCompCap): keys and parents in HBM, else in LDS.  A template
 // parameter, so that every pointer below has one address space (LDS through
@@ -2478,7 +2464,7 @@ __device__ __forceinline__ void noise_group_sheet(const NoiseGeom& g, const Nois
   for (int i = tid; i <= nb; i += kGroupThreads) bc[i] = 0;
   __syncthreads();
   for (int i = tid; i < (int)n; i += kGroupThreads) {
-    if (NCHK(((NP.seq[i] >> 16) >> b) < (uint32_t)nb, 1, NP.seq[i])) atomicAdd(&bc[(NP.seq[i] >> 16) >> b], 1u);
+    atomicAdd(&bc[(NP.seq[i] >> 16) >> b], 1u);
   }
   __syncthreads();
   // exclusive scan of the nb counts: KB consecutive buckets a thread
@@ -2534,7 +2520,7 @@ __device__ __forceinline__ void noise_group_sheet(const NoiseGeom& g, const Nois
   for (int i = tid; i < (int)n; i += kGroupThreads) {
     const uint32_t key = NP.seq[i];
     const uint32_t dst = atomicAdd(&cur[(key >> 16) >> b], 1u);
-    if (NCHK(dst < n, 2, dst)) keys[dst] = key;
+    keys[dst] = key;
   }
   __threadfence_block();
   __syncthreads();
@@ -2558,7 +2544,6 @@ __device__ __forceinline__ void noise_group_sheet(const NoiseGeom& g, const Nois
   for (int q = 0, k = 0; nl > 0 && (nl <= kLongList ? q < nl : k < nb);) {
     const int kb = nl <= kLongList ? (int)longs[q++] : k++;  // uniform
     const int lo = (int)bc[kb], len = (int)bc[kb + 1] - lo;
-    if (!NCHK(kb < nb && lo + len <= (int)n, 3, kb)) continue;
     if (len <= kGroupBucketMax) continue;
     int p2 = 1;
     while (p2 < len) p2 <<= 1;
@@ -2590,7 +2575,6 @@ __device__ __forceinline__ void noise_group_sheet(const NoiseGeom& g, const Nois
   for (int i = tid; i < (int)n; i += kGroupThreads) {
     const uint32_t key = keys[i];
     const int32_t x = (int32_t)(key & 0xFFFF), y = (int32_t)(key >> 16);
-    if (!NCHK(y < g.H && (imax(y - R, 0) >> b) < nb, 4, key)) continue;
     for (int j = (int)bc[imax(y - R, 0) >> b]; j < i; j++) {
       const uint32_t kj = keys[j];
       const int32_t xj = (int32_t)(kj & 0xFFFF), yj = (int32_t)(kj >> 16);
@@ -2606,7 +2590,6 @@ __device__ __forceinline__ void noise_group_sheet(const NoiseGeom& g, const Nois
     for (int i = tid; i < (int)n; i += kGroupThreads) {
       gk[i] = keys[i];
       gk[kCompCap + i] = uf_find(par, (uint32_t)i);
-      (void)NCHK(gk[kCompCap + i] < n, 5, gk[kCompCap + i]);
     }
     __syncthreads();
     for (int i = tid; i < (int)n; i += kGroupThreads) keys[i] = 0u;
@@ -2672,18 +2655,10 @@ __global__ void __launch_bounds__(T) k_noise_group(PlaneRef img, NoiseGeom g, ui
     noise_group_sheet<FMT, T, false>(g, NP, gk, glds, base, pitch, flag, n, bb);
 }
 
-#ifndef UPH_REPLAY_WAVES
-// > 0: k_noise_replay's register budget in waves a SIMD (A/B: 6 waves 131 ->
-// 144 us a C3 launch, C4 noisefilter 0.82 -> 0.88 ms; 8 waves worse: off)
-#define UPH_REPLAY_WAVES 0
-#endif
-#if UPH_REPLAY_WAVES > 0
-#define UPH_REPLAY_ATTR __attribute__((amdgpu_waves_per_eu(UPH_REPLAY_WAVES)))
-#else
-#define UPH_REPLAY_ATTR
-#endif
+// No waves-per-SIMD hint (A/B: a budget of 6 waves 131 -> 144 us a C3 launch,
+// C4 noisefilter 0.82 -> 0.88 ms; 8 waves worse).
 template <int FMT>
-__global__ void __launch_bounds__(256) UPH_REPLAY_ATTR k_noise_replay(PlaneRef img, NoiseGeom g, uint8_t* scratch,
+__global__ void __launch_bounds__(256) k_noise_replay(PlaneRef img, NoiseGeom g, uint8_t* scratch,
                                                       int64_t sstride, const int32_t* active,
                                                       const uint32_t* sortbuf, int64_t sort_stride,
                                                       int kCompCap) {

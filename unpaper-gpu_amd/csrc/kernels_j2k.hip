@@ -147,221 +147,32 @@ __device__ __forceinline__ int wave_max(int v) {
   return v;
 }
 
-// Flag rows of groups up to 64 blocks wide go through LDS: a ring of four
-// stripe rows (the stripes above, at and below the one being decoded, and
-// the next one arriving), each row the 64 lanes' words of Wg + 2 columns.
-// 0: flags straight from the slot (measured faster: 6 waves a SIMD hide the
-// slot's latency better than the ring's LDS lets one wave a SIMD hide
-// nothing; 209 vs 293 ms per 32-page launch)
-#ifndef UPH_T1_RING
-#define UPH_T1_RING 0
-#endif
-constexpr int kRingCols = UPH_T1_RING ? 66 : 0;
-constexpr int kRingRow = kRingCols * 64;  // uint16 words
-
-// one flag row between the scratch slot (global) and a ring row (LDS), as
-// 16-byte chunks across the lanes (the layouts are the same)
-__device__ __forceinline__ void t1_row_load(const uint16_t* g, int ws, uint4 (&r)[9]) {
-  const int n16 = ws * 8;  // 16-byte chunks in the row (ws * 64 words)
-#pragma unroll
-  for (int i = 0; i < 9; i++) {
-    const int ch = i * 64 + threadIdx.x;
-    if (ch < n16) r[i] = reinterpret_cast<const uint4*>(g)[ch];
-  }
-}
-__device__ __forceinline__ void t1_row_put(uint16_t* l, int ws, const uint4 (&r)[9]) {
-  const int n16 = ws * 8;
-#pragma unroll
-  for (int i = 0; i < 9; i++) {
-    const int ch = i * 64 + threadIdx.x;
-    if (ch < n16) reinterpret_cast<uint4*>(l)[ch] = r[i];
-  }
-}
-__device__ __forceinline__ void t1_row_store(uint16_t* g, int ws, const uint16_t* l) {
-  const int n16 = ws * 8;
-#pragma unroll
-  for (int i = 0; i < 9; i++) {
-    const int ch = i * 64 + threadIdx.x;
-    if (ch < n16) reinterpret_cast<uint4*>(g)[ch] = reinterpret_cast<const uint4*>(l)[ch];
-  }
-}
-
-// t1_decode_lane with the flag rows in the LDS ring (groups with Wg <= 64):
-// each pass loads the first three rows, then per stripe prefetches the row
-// two below into registers, decodes the stripe from LDS, writes the stripe's
-// row back to the slot and puts the prefetched row in the freed ring row.
-// The rows cross lanes on their way (16-byte chunks), so the slot's writes
-// and the next pass's reads are ordered by the workgroup (one wave) barrier.
-__device__ __attribute__((noinline)) void t1_decode_ring(T1Lane<64>& L, bool active, const uint8_t* data, int numbps,
-                               int npasses, int Sg, int maxpasses, uint16_t* ring,
-                               uint16_t* gfl) {
-  const int lane = threadIdx.x;
-  const int WS = L.WS;
-  for (int i = lane; i < (Sg + 2) * WS * 8; i += 64) reinterpret_cast<uint4*>(gfl)[i] = make_uint4(0, 0, 0, 0);
-  L.pm = 1 << 30;
-  if (active) {
-    L.reset_contexts();
-    L.mq_init(data);
-  }
-  __syncthreads();
-  for (int k = 0; k < maxpasses; k++) {
-    int type, bpno;
-    t1_pass(k, numbps, &type, &bpno);
-    const bool on = active && k < npasses && bpno >= 1;
-    if (__ballot(on) == 0) continue;
-    if (on && type == 1) L.pm = bpno;
-    {
-      uint4 r[9];
-      for (int R = 0; R < 3 && R <= Sg + 1; R++) {
-        t1_row_load(gfl + (int64_t)R * WS * 64, WS, r);
-        t1_row_put(ring + R * kRingRow, WS, r);
-      }
-    }
-    for (int s = 0; s < Sg; s++) {
-      const int R = s + 1;
-      uint4 pre[9];
-      const bool more = R + 2 <= Sg + 1;
-      if (more) t1_row_load(gfl + (int64_t)(R + 2) * WS * 64, WS, pre);
-      const uint16_t* U = ring + ((R - 1) & 3) * kRingRow + lane;
-      uint16_t* M = ring + (R & 3) * kRingRow + lane;
-      const uint16_t* D = ring + ((R + 1) & 3) * kRingRow + lane;
-      uint32_t Ul = 0, Ml = 0, Dl = 0;
-      uint32_t Uc = U[64], Mc = M[64], Dc = D[64];
-      uint32_t Ur = U[128], Mr = M[128], Dr = D[128];
-      const bool srow = on && 4 * s < L.h;
-      for (int col = 0; col < L.Wg; col++) {
-        uint32_t Un = 0, Mn = 0, Dn = 0;
-        if (col + 2 <= L.Wg) {
-          Un = U[(col + 3) * 64];
-          Mn = M[(col + 3) * 64];
-          Dn = D[(col + 3) * 64];
-        }
-        if (srow && col < L.w) {
-          L.column(type, bpno, s, col, Ul, Ml, Dl, Uc, &Mc, Dc, Ur, Mr, Dr);
-          M[(col + 1) * 64] = (uint16_t)Mc;
-        }
-        Ul = Uc;
-        Uc = Ur;
-        Ur = Un;
-        Ml = Mc;
-        Mc = Mr;
-        Mr = Mn;
-        Dl = Dc;
-        Dc = Dr;
-        Dr = Dn;
-      }
-      __builtin_amdgcn_wave_barrier();  // this wave's LDS writes land in order before its reads
-      t1_row_store(gfl + (int64_t)R * WS * 64, WS, ring + (R & 3) * kRingRow);
-      if (more) t1_row_put(ring + ((R + 2) & 3) * kRingRow, WS, pre);
-    }
-    __syncthreads();  // the rows written back before the next pass reads them
-  }
-}
-
-// The encoder's passes with the flag rows in the LDS ring (as
-// t1_decode_ring); the magnitudes' stripe-column words from the slot,
-// prefetched a column ahead.
-__device__ __attribute__((noinline)) int32_t t1_encode_ring(T1EncLane<64>& L, bool active, int nb, int Sg, int maxpasses,
-                                  uint16_t* ring, uint16_t* gfl) {
-  const int lane = threadIdx.x;
-  const int WS = L.WS;
-  if (active) {
-    L.reset_contexts();
-    L.init();
-  }
-  __syncthreads();  // the slot's preset flags (other lanes' chunks below)
-  for (int k = 0; k < maxpasses; k++) {
-    int type, p;
-    t1_pass(k, nb - 1, &type, &p);
-    const bool on = active && k < 3 * nb - 2;
-    if (__ballot(on) == 0) continue;
-    {
-      uint4 r[9];
-      for (int R = 0; R < 3 && R <= Sg + 1; R++) {
-        t1_row_load(gfl + (int64_t)R * WS * 64, WS, r);
-        t1_row_put(ring + R * kRingRow, WS, r);
-      }
-    }
-    for (int s = 0; s < Sg; s++) {
-      const int R = s + 1;
-      uint4 pre[9];
-      const bool more = R + 2 <= Sg + 1;
-      if (more) t1_row_load(gfl + (int64_t)(R + 2) * WS * 64, WS, pre);
-      const uint16_t* U = ring + ((R - 1) & 3) * kRingRow + lane;
-      uint16_t* M = ring + (R & 3) * kRingRow + lane;
-      const uint16_t* D = ring + ((R + 1) & 3) * kRingRow + lane;
-      uint32_t Ul = 0, Ml = 0, Dl = 0;
-      uint32_t Uc = U[64], Mc = M[64], Dc = D[64];
-      uint32_t Ur = U[128], Mr = M[128], Dr = D[128];
-      const bool srow = on && 4 * s < L.h;
-      uint64_t m4 = L.M4(s, 0), m4n = 0;
-      for (int col = 0; col < L.Wg; col++) {
-        uint32_t Un = 0, Mn = 0, Dn = 0;
-        if (col + 2 <= L.Wg) {
-          Un = U[(col + 3) * 64];
-          Mn = M[(col + 3) * 64];
-          Dn = D[(col + 3) * 64];
-        }
-        if (col + 1 < L.Wg) m4n = L.M4(s, col + 1);
-        if (srow && col < L.w) {
-          L.column(type, p, s, m4, Ul, Ml, Dl, Uc, &Mc, Dc, Ur, Mr, Dr);
-          M[(col + 1) * 64] = (uint16_t)Mc;
-        }
-        m4 = m4n;
-        Ul = Uc;
-        Uc = Ur;
-        Ur = Un;
-        Ml = Mc;
-        Mc = Mr;
-        Mr = Mn;
-        Dl = Dc;
-        Dc = Dr;
-        Dr = Dn;
-      }
-      __builtin_amdgcn_wave_barrier();
-      t1_row_store(gfl + (int64_t)R * WS * 64, WS, ring + (R & 3) * kRingRow);
-      if (more) t1_row_put(ring + ((R + 2) & 3) * kRingRow, WS, pre);
-    }
-    __syncthreads();
-  }
-  return active ? L.flush() : 0;
-}
-
 // Register budgets (waves a SIMD; 0: the compiler's choice, 98-105 VGPRs =
 // 4 waves): several code-block launches share the SIMDs, and each lane's
 // flag and context traffic is latency, so more resident waves pay even with
 // a few spilled registers (JP2 runner A/B: 4 -> 6 waves 847 -> 965-975
 // pages/s; 5 and 7 waves 927, 8 waves spill 124 bytes a lane: 772).  The
-// encoder at 6 waves measured no different (jp2_write 133 vs 134 pages/s).
+// encoder at 6 waves measured no different (jp2_write 133 vs 134 pages/s)
+// and carries no hint.
 #ifndef UPH_T1_WAVES
 #define UPH_T1_WAVES 6
-#endif
-#ifndef UPH_T1ENC_WAVES
-#define UPH_T1ENC_WAVES 0
 #endif
 #if UPH_T1_WAVES > 0
 #define UPH_T1_ATTR __attribute__((amdgpu_waves_per_eu(UPH_T1_WAVES)))
 #else
 #define UPH_T1_ATTR
 #endif
-#if UPH_T1ENC_WAVES > 0
-#define UPH_T1ENC_ATTR __attribute__((amdgpu_waves_per_eu(UPH_T1ENC_WAVES)))
-#else
-#define UPH_T1ENC_ATTR
-#endif
 
 // EBCOT code-block encode, a lane per block: the block's magnitudes and
 // preset signs into the slot (lane-minor), its plane count, then every pass
-// (flags through the LDS ring when the group is at most 64 wide); the
-// codeword into the job's output region.
-__global__ void __launch_bounds__(64) UPH_T1ENC_ATTR k_j2k_t1enc(const T1EncJob* jobs, int njobs,
+// (flags straight from the slot); the codeword into the job's output region.
+__global__ void __launch_bounds__(64) k_j2k_t1enc(const T1EncJob* jobs, int njobs,
                                                   const uint32_t* coef, uint8_t* dout,
                                                   uint32_t* dlen, uint8_t* dnb, uint8_t* scr,
                                                   int64_t slot_bytes, int64_t mg_off) {
   __shared__ MqState qe[47];
   __shared__ uint8_t zct[kZcTable];
   __shared__ uint8_t cxs[kNumCtx * 64];
-  __shared__ __attribute__((aligned(16))) uint16_t ring[UPH_T1_RING ? 4 * kRingRow : 8];
   const int lane = threadIdx.x;
   if (lane < 47) qe[lane] = kMq[lane];
   for (int i = lane; i < kZcTable; i += 64) {
@@ -423,11 +234,8 @@ __global__ void __launch_bounds__(64) UPH_T1ENC_ATTR k_j2k_t1enc(const T1EncJob*
     L.out = dout + job.out;
     L.cap = (int32_t)t1_enc_cap(job.w, job.h);
     L.over = false;  // (init() runs only for blocks with planes)
-    int32_t n;
-    if (WS <= kRingCols)
-      n = t1_encode_ring(L, active && nb > 0, nb, Sg, P, ring, reinterpret_cast<uint16_t*>(slot));
-    else
-      n = t1_encode_lane(L, active && nb > 0, nb, Sg, P, [](bool b) { return __ballot(b) != 0; });
+    const int32_t n =
+        t1_encode_lane(L, active && nb > 0, nb, Sg, P, [](bool b) { return __ballot(b) != 0; });
     if (active) {
       dlen[j] = L.over ? 0u : (uint32_t)n;
       if (mor < 0x10000u) dnb[j] = L.over ? 0xFE : (uint8_t)nb;  // > 16: refused by the host
@@ -485,15 +293,15 @@ __global__ void __launch_bounds__(256) k_j2k_gather(const T1EncJob* jobs, int nj
 
 // EBCOT code-block decode, a lane per block (j2k_t1_lane.h): the MQ tables
 // and the context bytes in LDS, flags in the block's scratch slot laid out
-// lane-minor (coalesced; through the LDS ring for groups up to 64 wide),
-// magnitude bits there too, the decoded block into the coefficients.
+// lane-minor (coalesced; straight from the slot: a ring of flag rows in LDS
+// measured 293 against 209 ms per 32-page launch), magnitude
+// bits there too, the decoded block into the coefficients.
 __global__ void __launch_bounds__(64) UPH_T1_ATTR k_j2k_t1(const T1Job* jobs, int njobs, const uint8_t* data,
                                                uint32_t* coef, uint8_t* scr, int64_t slot_bytes,
                                                int64_t val_off) {
   __shared__ MqState qe[47];
   __shared__ uint8_t zct[kZcTable];
   __shared__ uint8_t cxs[kNumCtx * 64];
-  __shared__ __attribute__((aligned(16))) uint16_t ring[UPH_T1_RING ? 4 * kRingRow : 8];
   const int lane = threadIdx.x;
   if (lane < 47) qe[lane] = kMq[lane];
   for (int i = lane; i < kZcTable; i += 64) {
@@ -520,12 +328,8 @@ __global__ void __launch_bounds__(64) UPH_T1_ATTR k_j2k_t1(const T1Job* jobs, in
     L.w = job.w;
     L.h = job.h;
     L.orient = job.orient;
-    if (Wg + 2 <= kRingCols)
-      t1_decode_ring(L, active, data + job.data, job.numbps, job.npasses, (Hg + 3) >> 2, P, ring,
-                     reinterpret_cast<uint16_t*>(slot));
-    else
-      t1_decode_lane(L, active, data + job.data, job.numbps, job.npasses, (Hg + 3) >> 2, P,
-                     [](bool b) { return __ballot(b) != 0; });
+    t1_decode_lane(L, active, data + job.data, job.numbps, job.npasses, (Hg + 3) >> 2, P,
+                   [](bool b) { return __ballot(b) != 0; });
     __syncthreads();  // flags written back (other lanes' chunks) before the store reads them
     t1_store_lane(L, active, job, coef, Hg);
   }

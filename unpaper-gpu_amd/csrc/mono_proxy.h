@@ -17,9 +17,6 @@
 
 namespace uph {
 
-void launch_copy_thr(const PlaneRef& src, const PlaneRef& dst, const CopyArgs* args, int count,
-                     int rows_hint, uint8_t thr, hipStream_t st);
-
 class MonoProxy {
  public:
   MonoProxy(const UphipImage& im, bool writes, const char* op) : orig_(im), writes_(writes) {

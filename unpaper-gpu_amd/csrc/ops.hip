@@ -13,19 +13,6 @@
 
 namespace uph {
 
-void launch_fill_thr(const PlaneRef& dst, const FillArgs* args, int count, int rows_hint,
-                     uint8_t thr, hipStream_t st);
-void launch_copy_thr(const PlaneRef& src, const PlaneRef& dst, const CopyArgs* args, int count,
-                     int rows_hint, uint8_t thr, hipStream_t st);
-void launch_apply_masks_thr(const PlaneRef& dst, const MaskArgs* args, int count, uint8_t thr,
-                            hipStream_t st);
-void launch_mirror_oop(const PlaneRef& src, const PlaneRef& dst, bool h, bool v, uint8_t thr,
-                       int count, hipStream_t st);
-void launch_rotate90_thr(const PlaneRef& src, const PlaneRef& dst, int direction, uint8_t thr,
-                         int count, hipStream_t st);
-void launch_stretch_thr(const PlaneRef& src, const PlaneRef& dst, int interp, uint8_t thr,
-                        int count, hipStream_t st);
-
 static bool ok_image(const UphipImage& im, const char* op) {
   if (!im.frame) return fail("%s: image has no frame", op);
   if (!runtime_ready()) return fail("%s: no HIP device", op);

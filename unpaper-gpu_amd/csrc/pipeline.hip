@@ -23,21 +23,6 @@
 
 namespace uph {
 
-void launch_fill_thr(const PlaneRef& dst, const FillArgs* args, int count, int rows_hint,
-                     uint8_t thr, hipStream_t st);
-void launch_copy_thr(const PlaneRef& src, const PlaneRef& dst, const CopyArgs* args, int count,
-                     int rows_hint, uint8_t thr, hipStream_t st);
-void launch_apply_masks_thr(const PlaneRef& dst, const MaskArgs* args, int count, uint8_t thr,
-                            hipStream_t st);
-void launch_mirror_oop(const PlaneRef& src, const PlaneRef& dst, bool h, bool v, uint8_t thr,
-                       int count, hipStream_t st);
-void launch_rotate90_thr(const PlaneRef& src, const PlaneRef& dst, int direction, uint8_t thr,
-                         int count, hipStream_t st);
-void launch_stretch_thr(const PlaneRef& src, const PlaneRef& dst, int interp, uint8_t thr,
-                        int count, hipStream_t st);
-void launch_shift(const PlaneRef& src, const PlaneRef& dst, int dx, int dy, const uint8_t bg[3],
-                  uint8_t thr, int count, hipStream_t st);
-
 // ---------------------------------------------------------------------------
 // control kernels (one thread per sheet)
 // ---------------------------------------------------------------------------
@@ -1059,12 +1044,9 @@ static bool border_rows_from_center(const UphipBatch* b) {
 // (launch_move_chain): the centring only counts (a dry pass, C is never
 // written) and the align move gathers straight from the uncentred plane.
 // Needs border_rows_from_center, one page (one centring move), the align move
-// on, and 32-bit plane offsets.
-#ifndef UPH_CHAIN_MOVES
-#define UPH_CHAIN_MOVES 1  // 0: the two moves as separate passes (A/B builds)
-#endif
+// on, and 32-bit plane offsets; otherwise the two moves run as separate passes.
 static bool chain_center_align(const UphipBatch* b) {
-  if (!UPH_CHAIN_MOVES || !border_rows_from_center(b) || b->points.size() != 1) return false;
+  if (!border_rows_from_center(b) || b->points.size() != 1) return false;
   if (b->o.disable & UPHIP_NO_BORDER_ALIGN) return false;
   return b->pitch * (int64_t)b->H < (1ll << 31) && UPHIP_MAX_PAGES >= 2;
 }
@@ -1246,18 +1228,10 @@ static bool run_batch(UphipBatch* b, int count, const uint8_t* src, int64_t spit
   // what the fused decode hands on
   const bool black_on = !(dis & UPHIP_NO_BLACKFILTER) && b->bgeo.nbars > 0;
   const bool vsum_ready = fused && black_on && b->bgeo.vregion.x1 >= b->bgeo.vregion.x0;
-#ifndef UPH_NO_DECODE_RM
   const bool rm_ready = fused && black_on;  // the blackfilter's match plane from the decode
-#else
-  const bool rm_ready = false;
-#endif
   uint32_t* bits_ready = fused && !(dis & UPHIP_NO_NOISEFILTER) ? b->nbits : nullptr;
   // the blurfilter's plane: made by the decode, kept by the black/noise clears
-#ifndef UPH_NO_BLUR_BITS
   uint32_t* bb_ready = fused && !(dis & UPHIP_NO_BLURFILTER) ? b->bbits : nullptr;
-#else  // tuning A/B: the blur counts read the plane
-  uint32_t* bb_ready = nullptr;
-#endif
   if (fused) {
     launch_decode_gray(src, spitch, sstride, cur_ref(S0, b->ctl), o.abs_white_threshold, bits_ready,
                        b->nbits_stride, vsum_ready ? (uint32_t*)b->scr + b->bgeo.W : nullptr,
