@@ -335,6 +335,44 @@ def test_blur_counts_after_noise_and_black_clears(hip, oracle, white):
     check(oracle, opts, sheets, "blur bits")
 
 
+def test_fused_and_unfused_decode_agree(hip, oracle):
+    # The same four sheets from two device buffers: A with 256-multiple rows
+    # (the fused GRAY8 decode, which hands the blackfilter its row sums and
+    # match plane and the noise- and blurfilter their bit-planes) and B with
+    # tightly packed rows, which the plain copy decode takes and every filter
+    # computes its own inputs.  The ABI cannot report which decode ran: the
+    # test relies on decode_fused's alignment condition (pipeline.hip,
+    # `((uintptr_t)src & 15) || (spitch & 15) || (sstride & 15)` -> not fused),
+    # which B's pitch fails and A's buffer meets.
+    opts = oracle.default_options()
+    w, h = SMALL
+    pages = [speckled(w, h, p, k, 10 * p + k) for p, k in ((3, 40), (0, 70), (3, 90), (5, 110))]
+    n = len(pages)
+    pitches = ((w + 255) // 256 * 256, w)
+    assert pitches[0] % 16 == 0 and pitches[1] % 16 != 0
+    outs = []
+    for pitch in pitches:
+        host = np.zeros((n, h, pitch), np.uint8)
+        for s, p in enumerate(pages):
+            host[s, :, :w] = p.payload()
+        buf = DeviceBuffer(host.nbytes)
+        b = Batch(opts, n, w, h, A.FMT_GRAY8)
+        try:
+            assert buf.ptr % 16 == 0
+            assert buf.lib.uphip_memcpy_htod(buf.ptr, host.ctypes.data, host.nbytes) == 0
+            b.run_device(n, buf.ptr, pitch, pitch * h)
+            b.wait()
+            outs.append([b.output(s) for s in range(n)])
+        finally:
+            b.close()
+            buf.close()
+    fused, unfused = outs
+    for s in range(n):
+        assert_same(unfused[s], fused[s], "unfused vs fused sheet %d" % s)
+        exp, _ = oracle_sheet(oracle, opts, [pages[s]])
+        assert_same(fused[s], exp, "fused sheet %d" % s)
+
+
 def test_noisefilter_sequential_intensity(hip, oracle):
     opts = oracle.default_options()
     opts.noisefilter_intensity = 6

@@ -6,6 +6,28 @@
 
 namespace uph {
 
+// ---- what the page decode hands on -----------------------------------------
+// By-products of the fused GRAY8 decode (launch_decode_gray) that later
+// filters take instead of computing them; all zero: nothing handed on.  The
+// launchers pass them to F_GRAY8 planes only.
+struct SheetBits {
+  // the noisefilter's dark bit-plane (pixel < white) of the image as it
+  // stands, one u32 per 32 pixels, noise_bit_words(W) words a row: the
+  // blackfilter clears it where its fills paint, k_noise_bits is skipped
+  uint32_t* nbits = nullptr;
+  // the blurfilter's bit-plane (pixel <= white), same layout: the
+  // blackfilter's paints and every clear of the noisefilter clear it too, the
+  // block counts then read it instead of the plane (1/8 of the bytes).  Only
+  // where blur_bits_usable.
+  uint32_t* bbits = nullptr;
+  int64_t stride = 0;  // words per sheet, of both planes
+  // in the blackfilter's scratch: its v-stripe row sums (H entries per sheet
+  // after the W column sums) ...
+  bool vsum = false;
+  // ... and its row-major match plane (black_rm_plane)
+  bool rm = false;
+};
+
 // ---- grayfilter (filters.c:370-402) -------------------------------------
 // Tiles of scan_w x scan_h at origins (i*step_x, j*step_y) decompose exactly
 // into cells of gcd(step_x, scan_w) x gcd(step_y, scan_h) pixels.
@@ -26,7 +48,7 @@ size_t gray_scratch_bytes(const GrayGeom& g);  // per sheet
 // of the image the grayfilter leaves, added into colsum[s * colsum_stride + x]
 // (gray planes only).  Returns whether colsum was produced.
 bool launch_grayfilter(const PlaneRef& img, const GrayGeom& g, void* scratch,
-                       int64_t scratch_stride, const int32_t* active, int count, hipStream_t st,
+                       int64_t scratch_stride, int count, hipStream_t st,
                        uint32_t* colsum = nullptr, int64_t colsum_stride = 0);
 
 // ---- blurfilter (filters.c:149-232) -------------------------------------
@@ -42,13 +64,12 @@ struct BlurGeom {
 bool blur_geometry(int32_t W, int32_t H, const UphipBlurfilterParameters& p, uint8_t white,
                    BlurGeom* g);
 size_t blur_scratch_bytes(const BlurGeom& g);
-// bbits (optional): the GRAY8 bit-plane of pixels <= white of the image as it
-// stands (k_decode_gray made it, the blackfilter and noisefilter kept it
-// current), bb_stride words per sheet: the block counts then read it instead
-// of the plane (1/8 of the bytes).
+// Whether the block counts of a plane of format fmt can come from
+// SheetBits::bbits: the one condition for making the plane and for reading it
+// (it stays exact only while every clear makes a pixel > white).
+bool blur_bits_usable(const BlurGeom& g, int fmt);
 void launch_blurfilter(const PlaneRef& img, const BlurGeom& g, void* scratch,
-                       int64_t scratch_stride, const int32_t* active, int count, hipStream_t st,
-                       const uint32_t* bbits = nullptr, int64_t bb_stride = 0);
+                       int64_t scratch_stride, int count, hipStream_t st, const SheetBits& bits);
 
 // ---- noisefilter (filters.c:238-338) ------------------------------------
 struct NoiseGeom {
@@ -58,20 +79,16 @@ struct NoiseGeom {
   int32_t capacity;    // entries per list per sheet
   int32_t all_seq;
   int32_t diag;        // TEMP timing diagnostics
-  // optional: the blurfilter's GRAY8 bit-plane (pixel <= white, k_decode_gray),
-  // bb_stride words per sheet; every clear of the filter clears its bit too
+  // kernel side only: SheetBits::bbits and ::stride, set by launch_noisefilter
   uint32_t* bbits;
   int64_t bb_stride;
 };
 bool noise_geometry(int32_t W, int32_t H, uint64_t intensity, uint8_t white, NoiseGeom* g);
 size_t noise_scratch_bytes(const NoiseGeom& g);
-// bits (optional): the GRAY8 dark bit-plane of the image as it stands, one
-// u32 per 32 pixels, bits_stride words per sheet (k_decode_gray made it and
-// the blackfilter kept it current): k_noise_bits is then skipped.
 void launch_noisefilter(const PlaneRef& img, const NoiseGeom& g, void* scratch,
-                        int64_t scratch_stride, const int32_t* active, SheetCtl* ctl, int count,
-                        hipStream_t st, const uint32_t* bits = nullptr, int64_t bits_stride = 0);
-// 32-pixel words per row of the GRAY8 dark bit-plane
+                        int64_t scratch_stride, SheetCtl* ctl, int count, hipStream_t st,
+                        const SheetBits& bits);
+// 32-pixel words per row of the GRAY8 bit-planes
 inline int32_t noise_bit_words(int32_t W) { return (W + 31) >> 5; }
 
 // ---- blackfilter (filters.c:49-127, fill.c) -----------------------------
@@ -95,6 +112,13 @@ struct BlackGeom {
 bool black_geometry(int32_t W, int32_t H, const UphipBlackfilterParameters& p, uint8_t mask_max,
                     BlackGeom* g, BlackBar* bars, int max_bars);
 size_t black_scratch_bytes(const BlackGeom& g);
+void launch_blackfilter(const PlaneRef& img, const BlackGeom& g, const BlackBar* bars, void* scratch,
+                        int64_t ss, SheetCtl* ctl, int count, hipStream_t st, const AxisArgs* hargs,
+                        const AxisArgs* vargs, const SheetBits& bits);
+// The blackfilter's row-major match plane (RM: bit x of row y = gray <=
+// mask_max, 64-bit words, black_wpr words a row) of sheet 0 inside its
+// scratch; sheet s at + s * scratch_stride bytes.
+uint32_t* black_rm_plane(const BlackGeom& g, void* scratch);
 
 // ---- rotation detection (deskew.c:48-241) -------------------------------
 constexpr int kMaxAngles = 512;
@@ -124,31 +148,14 @@ const int32_t* rotation_line_flags(const int32_t* lines, int nlines, int max_sca
 int rotation_angles(const UphipDeskewParameters& p, RotTable* t);
 // Host: detect_rotation_cpu's combination of per-edge results (deskew.c:219-240)
 float combine_edge_rotations(const float* rot, int count, float deviation_rad);
-// vsum_ready: the v-stripe row sums are already in the scratch (k_decode_gray);
-// nbits (optional): the noisefilter's dark bit-plane, cleared where fills paint.
-void launch_blackfilter_impl(const PlaneRef& img, const BlackGeom& g, const BlackBar* bars,
-                             void* scratch, int64_t ss, const int32_t* active, SheetCtl* ctl,
-                             int count, hipStream_t st, const AxisArgs* hargs,
-                             const AxisArgs* vargs, bool vsum_ready = false,
-                             uint32_t* nbits = nullptr, int64_t nbits_stride = 0,
-                             uint32_t* bbits = nullptr, int64_t bb_stride = 0,
-                             bool rm_ready = false);
-// The blackfilter's row-major match plane (RM: bit x of row y = gray <=
-// mask_max, 64-bit words, black_wpr words a row) of sheet 0 inside its
-// scratch; sheet s at + s * scratch_stride bytes.  k_decode_gray can write it
-// (launch_blackfilter_impl's rm_ready).
-uint32_t* black_rm_plane(const BlackGeom& g, void* scratch);
-// GRAY8 page -> sheet plane (same size), plus on the way: the noisefilter's
-// dark bit-plane (pixel < white) and the blackfilter's v-stripe row sums over
-// columns [vx0, vx1] (vsum: H entries per sheet after W, vx0 > vx1 = none).
+
+// ---- page decode (sheet_stages.c:151-165) ---------------------------------
+// GRAY8 page -> sheet plane (same size), plus on the way what `bits` asks for:
+// its planes, and into the blackfilter's scratch (bg, black_scratch, sheet s
+// at + s * scratch_stride bytes) the v-stripe row sums and the RM plane.
 // Pages 16-byte aligned with a 16-multiple pitch.
-// bbits (optional): also the blurfilter's plane of pixels <= white, same layout
-// rm (optional): also the blackfilter's RM plane (pixel <= rm_max; rows of
-// 2 * ceil(W / 64) words, rm_stride words a sheet, black_rm_plane)
 void launch_decode_gray(const uint8_t* src, int64_t spitch, int64_t sstride, const PlaneRef& dst,
-                        uint8_t white, uint32_t* bits, int64_t bits_stride, uint32_t* vsum,
-                        int64_t vsum_stride, int32_t vx0, int32_t vx1, int count, hipStream_t st,
-                        uint32_t* bbits = nullptr, uint32_t* rm = nullptr, int64_t rm_stride = 0,
-                        uint8_t rm_max = 0);
+                        uint8_t white, const SheetBits& bits, const BlackGeom& bg,
+                        void* black_scratch, int64_t scratch_stride, int count, hipStream_t st);
 
 }  // namespace uph

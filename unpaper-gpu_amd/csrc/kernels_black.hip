@@ -128,10 +128,8 @@ __device__ __forceinline__ bool bar_candidate(const BlackGeom& g, const BlackBar
 // sheets get planes, a replay and a paint pass.
 constexpr int kCandThreads = 256;
 __global__ void __launch_bounds__(kCandThreads) k_black_cand(BlackGeom g, const BlackBar* bars,
-                                                             uint8_t* scratch, int64_t sstride,
-                                                             const int32_t* active) {
+                                                             uint8_t* scratch, int64_t sstride) {
   const int s = blockIdx.x;
-  if (active && !active[s]) return;
   uint8_t* scr = scratch + s * sstride;
   const uint32_t* hsum = (const uint32_t*)scr;
   uint8_t* head = scr + black_head_off(g);
@@ -160,9 +158,8 @@ __device__ __forceinline__ bool sheet_has_candidate(const BlackGeom& g, const ui
 // row words are read from it instead of from the image.
 template <int FMT, bool RM_READY>
 __global__ void __launch_bounds__(256) k_black_planes(PlaneRef img, BlackGeom g, uint8_t* scratch,
-                                                      int64_t sstride, const int32_t* active) {
+                                                      int64_t sstride) {
   const int s = blockIdx.z;
-  if (active && !active[s]) return;
   uint8_t* scr = scratch + s * sstride;
   if (!sheet_has_candidate(g, scr)) return;
   __shared__ uint64_t rw[64][4];
@@ -216,11 +213,10 @@ __global__ void __launch_bounds__(256) k_black_planes(PlaneRef img, BlackGeom g,
 // thread per row word.
 template <int FMT>
 __global__ void __launch_bounds__(256) k_black_paint(PlaneRef img, BlackGeom g, uint8_t* scratch,
-                                                     int64_t sstride, const int32_t* active,
-                                                     uint32_t* nbits, int64_t nbits_stride,
-                                                     uint32_t* bbits, int64_t bb_stride) {
+                                                     int64_t sstride, uint32_t* nbits,
+                                                     int64_t nbits_stride, uint32_t* bbits,
+                                                     int64_t bb_stride) {
   const int s = blockIdx.z;
-  if (active && !active[s]) return;
   uint8_t* scr = scratch + s * sstride;
   if (!sheet_has_candidate(g, scr)) return;
   const int32_t wpr = black_wpr(g);
@@ -926,10 +922,8 @@ __device__ __forceinline__ bool flood(const Sheet& S, int32_t sx, int32_t sy, Fr
 template <int FMT, bool LONG>
 __global__ void __launch_bounds__(64) k_black_resolve(PlaneRef img, BlackGeom g,
                                                       const BlackBar* bars, uint8_t* scratch,
-                                                      int64_t sstride, const int32_t* active,
-                                                      SheetCtl* ctl) {
+                                                      int64_t sstride, SheetCtl* ctl) {
   const int s = blockIdx.x;
-  if (active && !active[s]) return;
   uint8_t* scr = scratch + s * sstride;
   if (!sheet_has_candidate(g, scr)) return;
   const int lane = lane_id();
@@ -1091,24 +1085,21 @@ __global__ void __launch_bounds__(64) k_black_resolve(PlaneRef img, BlackGeom g,
 
 template <int FMT>
 static void launch_black_t(const PlaneRef& img, const BlackGeom& g, const BlackBar* bars,
-                           uint8_t* scr, int64_t ss, const int32_t* active, SheetCtl* ctl,
-                           int count, hipStream_t st, const AxisArgs* hargs,
-                           const AxisArgs* vargs, bool vsum_ready, uint32_t* nbits,
-                           int64_t nbits_stride, uint32_t* bbits, int64_t bb_stride,
-                           bool rm_ready) {
+                           uint8_t* scr, int64_t ss, SheetCtl* ctl, int count, hipStream_t st,
+                           const AxisArgs* hargs, const AxisArgs* vargs, const SheetBits& bits) {
   // column sums of max(rgb) over the h-stripe rows, row sums over the v-stripe cols
   if (g.hregion.x1 >= g.hregion.x0 && g.hregion.y1 >= g.hregion.y0)
     launch_axis_reduce(img, hargs, 0, M_DARKINV_SUM, g.W, g.H, (uint32_t*)scr, ss / 4, count, st);
-  if (g.vregion.x1 >= g.vregion.x0 && g.vregion.y1 >= g.vregion.y0 && !vsum_ready)
+  if (g.vregion.x1 >= g.vregion.x0 && g.vregion.y1 >= g.vregion.y0 && !bits.vsum)
     launch_axis_reduce(img, vargs, 1, M_DARKINV_SUM, g.vregion.x1 - g.vregion.x0 + 1, g.H,
                        (uint32_t*)scr + g.W, ss / 4, count, st);
-  hipLaunchKernelGGL(k_black_cand, dim3(count), dim3(kCandThreads), 0, st, g, bars, scr, ss, active);
-  if (FMT == F_GRAY8 && rm_ready)
+  hipLaunchKernelGGL(k_black_cand, dim3(count), dim3(kCandThreads), 0, st, g, bars, scr, ss);
+  if (FMT == F_GRAY8 && bits.rm)
     hipLaunchKernelGGL((k_black_planes<FMT, true>), dim3((black_wpr(g) + 3) / 4, black_hpc(g), count),
-                       dim3(256), 0, st, img, g, scr, ss, active);
+                       dim3(256), 0, st, img, g, scr, ss);
   else
     hipLaunchKernelGGL((k_black_planes<FMT, false>), dim3((black_wpr(g) + 3) / 4, black_hpc(g), count),
-                       dim3(256), 0, st, img, g, scr, ss, active);
+                       dim3(256), 0, st, img, g, scr, ss);
   BlackGeom gd = g;
   gd.diag = diag_noise();
   // LONG: the long-line machinery (open fill lines sharing the wave, planned
@@ -1122,16 +1113,16 @@ static void launch_black_t(const PlaneRef& img, const BlackGeom& g, const BlackB
     if (longl) {
       allow_dynamic_lds((const void*)k_black_resolve<FMT, true>, kStackLdsBytes);
       hipLaunchKernelGGL((k_black_resolve<FMT, true>), dim3(count), dim3(64), kStackLdsBytes, st, img, gd,
-                         bars, scr, ss, active, ctl);
+                         bars, scr, ss, ctl);
     } else {
       allow_dynamic_lds((const void*)k_black_resolve<FMT, false>, kStackLdsBytes);
       hipLaunchKernelGGL((k_black_resolve<FMT, false>), dim3(count), dim3(64), kStackLdsBytes, st, img, gd,
-                         bars, scr, ss, active, ctl);
+                         bars, scr, ss, ctl);
     }
   }
   hipLaunchKernelGGL(k_black_paint<FMT>, dim3((black_wpr(g) + 63) / 64, (g.H + 3) / 4, count),
-                     dim3(256), 0, st, img, g, scr, ss, active, FMT == F_GRAY8 ? nbits : nullptr,
-                     nbits_stride, FMT == F_GRAY8 ? bbits : nullptr, bb_stride);
+                     dim3(256), 0, st, img, g, scr, ss, bits.nbits, bits.stride, bits.bbits,
+                     bits.stride);
 }
 
 uint32_t* black_rm_plane(const BlackGeom& g, void* scratch) {
@@ -1146,26 +1137,20 @@ __global__ void k_black_prep(uint8_t* scr, int64_t ss, int32_t words, int count)
     p[i] = 0;
 }
 
-void launch_blackfilter_impl(const PlaneRef& img, const BlackGeom& g, const BlackBar* bars,
-                             void* scratch, int64_t ss, const int32_t* active, SheetCtl* ctl,
-                             int count, hipStream_t st, const AxisArgs* hargs,
-                             const AxisArgs* vargs, bool vsum_ready, uint32_t* nbits,
-                             int64_t nbits_stride, uint32_t* bbits, int64_t bb_stride,
-                             bool rm_ready) {
+void launch_blackfilter(const PlaneRef& img, const BlackGeom& g, const BlackBar* bars, void* scratch,
+                        int64_t ss, SheetCtl* ctl, int count, hipStream_t st, const AxisArgs* hargs,
+                        const AxisArgs* vargs, const SheetBits& bits) {
   uint8_t* scr = (uint8_t*)scratch;
   hipLaunchKernelGGL(k_black_prep, dim3(8, count), dim3(256), 0, st, scr, ss, g.W, count);
   switch (img.P.fmt) {
     case F_GRAY8:
-      launch_black_t<F_GRAY8>(img, g, bars, scr, ss, active, ctl, count, st, hargs, vargs,
-                              vsum_ready, nbits, nbits_stride, bbits, bb_stride, rm_ready);
+      launch_black_t<F_GRAY8>(img, g, bars, scr, ss, ctl, count, st, hargs, vargs, bits);
       break;
     case F_Y400A:
-      launch_black_t<F_Y400A>(img, g, bars, scr, ss, active, ctl, count, st, hargs, vargs,
-                              vsum_ready, nbits, nbits_stride, bbits, bb_stride, rm_ready);
+      launch_black_t<F_Y400A>(img, g, bars, scr, ss, ctl, count, st, hargs, vargs, {});
       break;
     default:
-      launch_black_t<F_RGB24>(img, g, bars, scr, ss, active, ctl, count, st, hargs, vargs,
-                              vsum_ready, nbits, nbits_stride, bbits, bb_stride, rm_ready);
+      launch_black_t<F_RGB24>(img, g, bars, scr, ss, ctl, count, st, hargs, vargs, {});
       break;
   }
 }

@@ -97,7 +97,7 @@ void uphip_grayfilter(UphipImage image0, UphipGrayfilterParameters params) {
   hipStream_t st = current_stream();
   void* scr = scratch(2, gray_scratch_bytes(g));
   if (!scr) return;
-  launch_grayfilter(ref1(image.frame), g, scr, 0, nullptr, 1, st);
+  launch_grayfilter(ref1(image.frame), g, scr, 0, 1, st);
   mp.finish();
 }
 
@@ -113,7 +113,7 @@ void uphip_blurfilter(UphipImage image0, UphipBlurfilterParameters params,
     return (void)fail("blurfilter: invalid scan size");
   void* scr = scratch(2, blur_scratch_bytes(g));
   if (!scr) return;
-  launch_blurfilter(ref1(image.frame), g, scr, 0, nullptr, 1, current_stream());
+  launch_blurfilter(ref1(image.frame), g, scr, 0, 1, current_stream(), SheetBits{});
   mp.finish();
 }
 
@@ -132,7 +132,7 @@ void uphip_noisefilter(UphipImage image0, uint64_t intensity, uint8_t min_white_
   if (!scr || !ctl) return;
   hipStream_t st = current_stream();
   UPH_HIP(hipMemsetAsync(ctl, 0, sizeof(SheetCtl), st));
-  launch_noisefilter(ref1(image.frame), g, scr, (int64_t)bytes, nullptr, ctl, 1, st);
+  launch_noisefilter(ref1(image.frame), g, scr, (int64_t)bytes, ctl, 1, st, SheetBits{});
   int32_t status = 0;
   UPH_HIP(hipMemcpyAsync(&status, &ctl->status, 4, hipMemcpyDeviceToHost, st));
   UPH_HIP(hipStreamSynchronize(st));
@@ -168,8 +168,8 @@ void uphip_blackfilter(UphipImage image0, UphipBlackfilterParameters params) {
   AxisArgs* dah = stage_args(&ah, 1, st);
   AxisArgs* dav = stage_args(&av, 1, st);
   if (!dah || !dav) return;
-  launch_blackfilter_impl(ref1(image.frame), g, dbars, scr, (int64_t)bytes, nullptr, ctl, 1, st,
-                          dah, dav);
+  launch_blackfilter(ref1(image.frame), g, dbars, scr, (int64_t)bytes, ctl, 1, st, dah, dav,
+                     SheetBits{});
   arg_fence(st);
   int32_t status = 0;
   UPH_HIP(hipMemcpyAsync(&status, &ctl->status, 4, hipMemcpyDeviceToHost, st));

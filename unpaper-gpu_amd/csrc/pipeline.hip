@@ -751,9 +751,7 @@ static bool allocate(UphipBatch* b) {
     if (!blur_geometry(W, H, o.blurfilter_parameters, o.abs_white_threshold, &b->blgeo))
       return fail("batch: invalid blurfilter parameters");
     need = std::max(need, blur_scratch_bytes(b->blgeo));
-    // the bit-plane stays exact only while every clear makes a pixel > white
-    if (b->work_fmt == F_GRAY8 && o.abs_white_threshold < 255 && b->blgeo.nrect > 0 &&
-        b->blgeo.sw >= 32) {
+    if (blur_bits_usable(b->blgeo, b->work_fmt)) {
       b->nbits_stride = ((int64_t)noise_bit_words(W) * H + 63) & ~(int64_t)63;
       b->bbits = dalloc<uint32_t>(b, (size_t)b->nbits_stride * cap);
       if (!b->bbits) return false;
@@ -1225,19 +1223,16 @@ static bool run_batch(UphipBatch* b, int count, const uint8_t* src, int64_t spit
   Planes S0 = planes_of(b, w, h);
   const bool covered = n == 1 && b->rp_w == w && b->rp_h == h;
   const bool fused = decode_fused(b, src, spitch, sstride);
-  // what the fused decode hands on
-  const bool black_on = !(dis & UPHIP_NO_BLACKFILTER) && b->bgeo.nbars > 0;
-  const bool vsum_ready = fused && black_on && b->bgeo.vregion.x1 >= b->bgeo.vregion.x0;
-  const bool rm_ready = fused && black_on;  // the blackfilter's match plane from the decode
-  uint32_t* bits_ready = fused && !(dis & UPHIP_NO_NOISEFILTER) ? b->nbits : nullptr;
-  // the blurfilter's plane: made by the decode, kept by the black/noise clears
-  uint32_t* bb_ready = fused && !(dis & UPHIP_NO_BLURFILTER) ? b->bbits : nullptr;
+  SheetBits bits;  // what the fused decode hands on
   if (fused) {
-    launch_decode_gray(src, spitch, sstride, cur_ref(S0, b->ctl), o.abs_white_threshold, bits_ready,
-                       b->nbits_stride, vsum_ready ? (uint32_t*)b->scr + b->bgeo.W : nullptr,
-                       b->scr_stride / 4, b->bgeo.vregion.x0, b->bgeo.vregion.x1, count, b->st,
-                       bb_ready, rm_ready ? black_rm_plane(b->bgeo, b->scr) : nullptr,
-                       b->scr_stride / 4, b->bgeo.mask_max);
+    const bool black_on = !(dis & UPHIP_NO_BLACKFILTER) && b->bgeo.nbars > 0;
+    bits.nbits = !(dis & UPHIP_NO_NOISEFILTER) ? b->nbits : nullptr;
+    bits.bbits = !(dis & UPHIP_NO_BLURFILTER) ? b->bbits : nullptr;
+    bits.stride = b->nbits_stride;
+    bits.vsum = black_on && b->bgeo.vregion.x1 >= b->bgeo.vregion.x0;
+    bits.rm = black_on;
+    launch_decode_gray(src, spitch, sstride, cur_ref(S0, b->ctl), o.abs_white_threshold, bits,
+                       b->bgeo, b->scr, b->scr_stride, count, b->st);
   }
   if (!covered) fill_uniform(b, S0, 0, Rect{0, 0, w - 1, h - 1}, o.sheet_background, count);
   for (int j = 0; j < n && !fused; j++) {
@@ -1318,22 +1313,17 @@ static bool run_batch(UphipBatch* b, int count, const uint8_t* src, int64_t spit
   mark(b, "pre");
   // ---- filters (sheet_stages.c:327-357) ---------------------------------
   if (!(dis & UPHIP_NO_BLACKFILTER) && b->bgeo.nbars > 0) {
-    launch_blackfilter_impl(cur_ref(P, b->ctl), b->bgeo, b->dbars, b->scr, b->scr_stride, nullptr,
-                            b->ctl, count, b->st, b->black_h, b->black_v, vsum_ready, bits_ready,
-                            b->nbits_stride, bb_ready, b->nbits_stride, rm_ready);
+    launch_blackfilter(cur_ref(P, b->ctl), b->bgeo, b->dbars, b->scr, b->scr_stride, b->ctl, count,
+                       b->st, b->black_h, b->black_v, bits);
     mark(b, "blackfilter");
   }
   if (!(dis & UPHIP_NO_NOISEFILTER)) {
-    NoiseGeom ng = b->ngeo;
-    ng.bbits = bb_ready;
-    ng.bb_stride = b->nbits_stride;
-    launch_noisefilter(cur_ref(P, b->ctl), ng, b->scr, b->scr_stride, nullptr, b->ctl, count,
-                       b->st, bits_ready, b->nbits_stride);
+    launch_noisefilter(cur_ref(P, b->ctl), b->ngeo, b->scr, b->scr_stride, b->ctl, count, b->st,
+                       bits);
     mark(b, "noisefilter");
   }
   if (!(dis & UPHIP_NO_BLURFILTER)) {
-    launch_blurfilter(cur_ref(P, b->ctl), b->blgeo, b->scr, b->scr_stride, nullptr, count, b->st,
-                      bb_ready, b->nbits_stride);
+    launch_blurfilter(cur_ref(P, b->ctl), b->blgeo, b->scr, b->scr_stride, count, b->st, bits);
     mark(b, "blurfilter");
   }
   bool mask_sums_ready = false;
@@ -1347,8 +1337,8 @@ static bool run_batch(UphipBatch* b, int count, const uint8_t* src, int64_t spit
       UPH_HIP(hipMemsetAsync(b->sums, 0, sizeof(uint32_t) * b->sums_stride * count, b->st));
       cs = b->sums;  // point 0, horizontal: offset 0
     }
-    mask_sums_ready = launch_grayfilter(cur_ref(P, b->ctl), b->ggeo, b->scr, b->scr_stride, nullptr,
-                                        count, b->st, cs, b->sums_stride);
+    mask_sums_ready = launch_grayfilter(cur_ref(P, b->ctl), b->ggeo, b->scr, b->scr_stride, count,
+                                        b->st, cs, b->sums_stride);
     mark(b, "grayfilter");
   }
   // ---- deskew (sheet_stages.c:388-413) ---------------------------------
