@@ -183,17 +183,25 @@ inline uint32_t div_magic(uint32_t d) { return d > 1 ? (uint32_t)(0xFFFFFFFFull 
 __device__ __forceinline__ int div_by_magic(int n, uint32_t m) {
   return m ? (int)__umulhi((uint32_t)n, m) : n;
 }
+// *lin_t: the tile's linear index (bz * gy + by) * gx + bx, known before the
+// divisions.
 __device__ __forceinline__ void xcd_block_m(uint32_t m_gxy, uint32_t m_gx, int* bx, int* by,
-                                            int* bz) {
+                                            int* bz, int* lin_t) {
   const int gx = gridDim.x, gy = gridDim.y;
   const int nblk = gx * gy * gridDim.z;
   const int lin = blockIdx.x + gx * (blockIdx.y + gy * blockIdx.z);
   const int q = nblk >> 3, rr = nblk & 7, xcd = lin & 7;
   const int t = xcd * q + (xcd < rr ? xcd : rr) + (lin >> 3);
+  *lin_t = t;
   *bz = div_by_magic(t, m_gxy);
   const int rem = t - *bz * gx * gy;
   *by = div_by_magic(rem, m_gx);
   *bx = rem - *by * gx;
+}
+__device__ __forceinline__ void xcd_block_m(uint32_t m_gxy, uint32_t m_gx, int* bx, int* by,
+                                            int* bz) {
+  int t;
+  xcd_block_m(m_gxy, m_gx, bx, by, bz, &t);
 }
 
 // ---------------------------------------------------------------------------

@@ -129,9 +129,13 @@ bool launch_move_rect_fused(const PlaneRef& src, const PlaneRef& dst, const Move
 // colsum (optional, zeroed by the caller for the rotated sheets): the
 // output's column sums over all rows added into colsum[s * cs_stride + x];
 // returns whether they were (GRAY8 cubic, staged window only).
+// scratch: rotate_scratch_bytes(W, H, count) bytes of device memory, 256-byte
+// aligned, the launch's own until it has run (the GRAY8 bicubic rotation's
+// per-sheet and per-tile records, written by a small kernel of the launch).
+size_t rotate_scratch_bytes(int32_t W, int32_t H, int count);
 bool launch_rotate_mask(const PlaneRef& src, const PlaneRef& dst, const RotateArgs* args,
                         int interp, int count, hipStream_t st, float max_abs_angle,
-                        uint32_t* colsum = nullptr, int64_t cs_stride = 0);
+                        void* scratch, uint32_t* colsum = nullptr, int64_t cs_stride = 0);
 // Bilinear rotation (kernels_rotlin.hip), GRAY8 and RGB24: up to two masks
 // per sheet, args[m * mstride + s]; mask m >= 1 only where indep[s] (or
 // indep == null).  Sheets with no active mask are left alone (not flipped).

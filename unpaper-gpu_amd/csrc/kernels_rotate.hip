@@ -7,6 +7,7 @@
 #include "blit_common.h"
 #include "interp.h"
 #include "kernels.h"
+#include "rot_tiles.h"
 
 namespace uph {
 
@@ -571,9 +572,7 @@ __global__ void __launch_bounds__(kThreads) k_rotate_cubic_g8(PlaneRef src, Plan
 // Every rounding operation of cubic_scale (interpolate.c:24-31) stays a
 // separate multiply or add in the reference's order, as in cubic2.
 // ---------------------------------------------------------------------------
-constexpr int kRFW = 128;   // output columns per tile (2 per lane)
-constexpr int kRFH = 48;    // output rows per tile, 6 per wave (96-row tiles measured slower: DESIGN §5)
-constexpr int kRFS = 144;   // staged row stride in floats (>= 141-float window rows at 5 deg)
+// kRFW x kRFH output tiles, kRFS floats a staged row: rot_tiles.h
 constexpr int kRFT = 512;   // threads per tile: 8 waves, kRFH / 8 consecutive rows each
 constexpr int kRFWaves = kRFT / 64;
 
@@ -672,49 +671,106 @@ __device__ unsigned long long g_rot_phase[1024 * 8];
 #else
 #define UPH_ROT_T(k)
 #endif
+// The sheet's planes come out of its record, so the compiler cannot see that
+// they are global memory: without these, every access through them becomes a
+// flat instruction (which also counts as an LDS operation in the waits).
+template <class T>
+__device__ __forceinline__ T gload(const uint8_t* p) {
+  return *(const __attribute__((address_space(1))) T*)p;
+}
+template <class T>
+__device__ __forceinline__ void gstore(uint8_t* p, T v) {
+  *(__attribute__((address_space(1))) T*)p = v;
+}
+
+// The plane's geometry: what the kernel needs of Planes (pitch * H < 2^31).
+struct RotPlane {
+  int32_t W, H;
+  uint32_t pitch;
+};
+
+// The per-sheet constants, the window and the class of every tile of every
+// active sheet (rot_tiles.h), written once per launch so that the rotation's
+// tiles read them instead of deriving them.  One thread per tile, one block
+// row per sheet; block (0, 0) also counts the launch's large-window sheets.
+//   cls_rows: 0 = one launch takes every sheet with rows_small window rows;
+//   else sheets that need more than cls_rows rows are `large` (rows_large).
+__global__ void __launch_bounds__(256) k_rot_tiles(PlaneRef src, PlaneRef dst, const RotateArgs* args,
+                                                   int count, int tgx, int tgy, int rows_small,
+                                                   int rows_large, int cls_rows, RotSheet* sheets,
+                                                   RotTile* tiles, uint32_t* nlarge) {
+  const int s = blockIdx.y;
+  if (blockIdx.x == 0 && s == 0) {
+    __shared__ uint32_t n_s;
+    if (threadIdx.x == 0) n_s = 0;
+    __syncthreads();
+    uint32_t c = 0;
+    if (cls_rows)
+      for (int q = threadIdx.x; q < count; q += blockDim.x)
+        c += args[q].active && rot_need_rows(args[q].sinval) > cls_rows;
+    if (c) atomicAdd(&n_s, c);
+    __syncthreads();
+    if (threadIdx.x == 0) *nlarge = n_s;
+  }
+  const RotateArgs a = args[s];
+  const bool first = blockIdx.x == 0 && threadIdx.x == 0;
+  if (!a.active) {  // the rotation reads no other field of an inactive sheet
+    if (first) sheets[s].active = 0, sheets[s].large = 0;
+    return;
+  }
+  RotSheet g;
+  rot_sheet_geom(a.mask.x0, a.mask.y0, a.mask.x1, a.mask.y1, a.sinval, a.cosval, &g);
+  g.src = plane_ptr(src, s);
+  g.dst = plane_ptr(dst, s);
+  g.active = 1;
+  g.large = cls_rows && rot_need_rows(a.sinval) > cls_rows;
+  if (first) sheets[s] = g;
+  const int ti = blockIdx.x * blockDim.x + threadIdx.x;
+  if (ti >= tgx * tgy) return;
+  const int tyi = ti / tgx;
+  tiles[(int64_t)s * (tgx * tgy) + ti] =
+      rot_tile(&g, src.P.W, src.P.H, ti - tyi * tgx, tyi, g.large ? rows_large : rows_small);
+}
+
+// sheets / tiles: k_rot_tiles' records of this launch; tiles[s * tiles-per-
+// sheet + tyi * (tiles per row) + txi].  LOOP: the large-window launch.
 template <bool LOOP>
-__global__ void __launch_bounds__(kRFT, UPH_ROT_MINB) k_rotate_cubic_g8f(PlaneRef src, PlaneRef dst,
-                                                               const RotateArgs* args,
-                                                               int max_rows, int cls_rows,
-                                                               int diag,
-                                                               uint32_t m_gxy, uint32_t m_gx,
-                                                               int loop_count, int tgx, int tgy,
-                                                               uint32_t* colsum, int64_t cs_stride) {
+__global__ void __launch_bounds__(kRFT, UPH_ROT_MINB) k_rotate_cubic_g8f(
+    const RotSheet* __restrict__ sheets, const RotTile* __restrict__ tiles,
+    const uint32_t* __restrict__ nlarge, RotPlane P, int max_rows, int diag, uint32_t m_gxy,
+    uint32_t m_gx, int loop_count, int tgx, int tgy, uint32_t* colsum, int64_t cs_stride) {
   // dynamic LDS: window [max_rows][kRFS] floats, nw[max_rows] u64, then one
   // (kRFH / 8) x kRFW byte output buffer per wave
   extern __shared__ __attribute__((aligned(16))) float winf[];
-  __shared__ int32_t win_s[4];
   // colsum (optional): the output's column sums over all rows, added into
   // colsum[s * cs_stride + x] (the next mask scan's, masks.c:54-209), so that
   // scan need not read the rotated plane again; per tile summed in LDS, then
   // one atomic per column
   __shared__ uint32_t csum_s[kRFW];
-  // one tile (txi, tyi) of sheet s; every return is block-uniform
-  auto tile = [&](int txi, int tyi, int s) {
+  // tile (txi, tyi) of sheet s, record ti; every return is block-uniform
+  auto tile = [&](int txi, int tyi, int s, int ti) {
 #ifdef UPHIP_DIAG
   unsigned long long tprev = wall_clock64();
 #endif
-  // the plane selectors and the arguments are loaded together (one round trip)
-  const uint8_t* sbase = plane_ptr(src, s);
-  uint8_t* dbase = plane_ptr(dst, s);
-  const RotateArgs a = args[s];
-  if (!a.active) return;
-  if (cls_rows != 0) {
-    // two launches split the sheets by the window rows their angle needs
-    // (cls_rows > 0: at most cls_rows; < 0: more than -cls_rows)
-    const int need = kRFH + (int)ceilf((kRFW - 1) * fabsf(a.sinval)) + 5;
-    if (cls_rows > 0 ? need > cls_rows : need <= -cls_rows) return;
-  }
-  const Planes& P = src.P;
-  const Rect nm = normalize(a.mask);
-  const int32_t sw = nm.x1 - nm.x0 + 1, sh = nm.y1 - nm.y0 + 1;
-  const float scx = nm.x0 + sw / 2.0f, scy = nm.y0 + sh / 2.0f;  // primitives.c:137-145
-  const float tcx = 0 + sw / 2.0f, tcy = 0 + sh / 2.0f;
+  // Both records sit at addresses made of the block index and the kernel's
+  // arguments alone: two independent scalar loads, one wait.  Nothing of the
+  // tile's geometry is derived here (rot_tiles.h, k_rot_tiles).
+  const RotTile T = tiles[ti];
+  const RotSheet a = sheets[s];
+  UPH_ROT_T(0)
+  // (both records wanted whole right here, before the first branch on one of
+  // their fields, and with them the arguments not fetched yet: otherwise the
+  // compiler fetches them piece by piece, each piece behind the branch that
+  // first needs it, one wait per piece)
+  asm volatile("" ::"s"(T.bx0), "s"((uint32_t)T.bw), "s"(T.flags), "s"(a.src), "s"(a.dst),
+               "s"(a.mx0), "s"(a.sw), "s"(a.scx), "s"(a.tcx), "s"(a.sinval), "s"(a.active),
+               "s"(P.W), "s"(P.H), "s"(P.pitch), "s"(colsum), "s"(cs_stride));
+  if (!a.active || (a.large != 0) != LOOP) return;  // each sheet: one of the two launches
+  const uint8_t* sbase = a.src;
+  uint8_t* dbase = a.dst;
+  const int32_t sw = a.sw, sh = a.sh;
+  const float scx = a.scx, scy = a.scy, tcx = a.tcx, tcy = a.tcy;
   const int32_t tx0 = txi * kRFW, ty0 = tyi * kRFH;
-  const int32_t u0 = imax(tx0, 0) - a.mask.x0, u1 = imin(tx0 + kRFW, P.W) - 1 - a.mask.x0;
-  const int32_t v0 = imax(ty0, 0) - a.mask.y0, v1 = imin(ty0 + kRFH, P.H) - 1 - a.mask.y0;
-  const int32_t cu0 = imax(u0, 0), cu1 = imin(u1, sw - 1);
-  const int32_t cv0 = imax(v0, 0), cv1 = imin(v1, sh - 1);
   // the tile's column sums (colsum): zeroed here, added per row below
   auto csum_flush = [&]() {
     __syncthreads();
@@ -722,15 +778,15 @@ __global__ void __launch_bounds__(kRFT, UPH_ROT_MINB) k_rotate_cubic_g8f(PlaneRe
       atomicAdd(colsum + s * cs_stride + tx0 + threadIdx.x, csum_s[threadIdx.x]);
   };
   // the tile's column sums zeroed; in-mask tiles need no barrier of their
-  // own here (the corners barrier below orders these writes before any
-  // wave's adds), so wave 0 starts on the corners while the block's other
-  // waves are still arriving
-  const bool outside_tile = !(cu0 <= cu1 && cv0 <= cv1);
+  // own here: the staging barrier below (taken by every in-mask tile, staged
+  // or not) orders these writes before any wave's adds, so every wave starts
+  // on its window loads as it arrives
+  const bool outside_tile = T.flags & ROT_T_OUTSIDE;
   if (colsum) {
     if (threadIdx.x < kRFW) csum_s[threadIdx.x] = 0;
     if (outside_tile) __syncthreads();
   }
-  if (!(cu0 <= cu1 && cv0 <= cv1)) {
+  if (outside_tile) {
     // no pixel of the tile inside the mask: copied unchanged (deskew.c:268-286)
     const int cb = 8 * (threadIdx.x & 15);
     const int32_t x = tx0 + cb;
@@ -741,14 +797,15 @@ __global__ void __launch_bounds__(kRFT, UPH_ROT_MINB) k_rotate_cubic_g8f(PlaneRe
       const uint8_t* sp = sbase + row_off(y, P.pitch) + x;
       uint8_t* dp = dbase + row_off(y, P.pitch) + x;
       if (x + 8 <= P.W) {
-        const uint64_t q = *reinterpret_cast<const uint64_t*>(sp);
-        *reinterpret_cast<uint64_t*>(dp) = q;
+        const uint64_t q = gload<uint64_t>(sp);
+        gstore<uint64_t>(dp, q);
 #pragma unroll
         for (int j = 0; j < 8; j++) cs8[j] += (uint32_t)(q >> (8 * j)) & 0xFFu;
       } else {
         for (int j = 0; x + j < P.W; j++) {
-          dp[j] = sp[j];
-          cs8[j & 7] += sp[j];
+          const uint8_t q = gload<uint8_t>(sp + j);
+          gstore<uint8_t>(dp + j, q);
+          cs8[j & 7] += q;
         }
       }
     }
@@ -759,44 +816,16 @@ __global__ void __launch_bounds__(kRFT, UPH_ROT_MINB) k_rotate_cubic_g8f(PlaneRe
     }
     return;
   }
-  UPH_ROT_T(0)
+  UPH_ROT_T(1)
   const int lane = threadIdx.x & 63;
   const int wu = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  // Source window of the tile's in-mask pixels (their 4x4 taps included).
-  // Every pixel's coordinate lies between the corners' (the same float
-  // expression, monotone in u and v); its taps span (int)c - 1 .. (int)c + 2,
-  // and (int)c <= floor(c) + 1 (truncation of negatives).  The window is a
-  // per-tile constant: wave 0 evaluates the four corners in lanes (c = lane
-  // & 3), reduces them across the quad and posts the bounds in LDS, instead
-  // of every wave running the float chain of all four corners.  (Every wave
-  // finding the bounds itself, with one barrier fewer and the column sums
-  // flushed by the last wave to arrive, measured slower: 1.11 vs 1.08 ms a
-  // 64-sheet launch)
-  if (wu == 0) {
-    const int c = lane & 3;
-    const int32_t u = c & 1 ? cu1 : cu0, v = c & 2 ? cv1 : cv0;
-    const float X = scx + (u - tcx) * a.cosval + (v - tcy) * a.sinval;
-    const float Y = scy + (v - tcy) * a.cosval - (u - tcx) * a.sinval;
-    float mnx = fminf(X, dpp_f<0xB1>(X)), mxx = fmaxf(X, dpp_f<0xB1>(X));
-    float mny = fminf(Y, dpp_f<0xB1>(Y)), mxy = fmaxf(Y, dpp_f<0xB1>(Y));
-    mnx = fminf(mnx, dpp_f<0x4E>(mnx));
-    mxx = fmaxf(mxx, dpp_f<0x4E>(mxx));
-    mny = fminf(mny, dpp_f<0x4E>(mny));
-    mxy = fmaxf(mxy, dpp_f<0x4E>(mxy));
-    if (lane < 4) {
-      const float q = lane == 0 ? mnx : lane == 1 ? mny : lane == 2 ? mxx : mxy;
-      win_s[lane] = (int32_t)floorf(q);
-    }
-  }
-  __syncthreads();
-  UPH_ROT_T(1)
-  const int32_t bx0 = __builtin_amdgcn_readfirstlane(win_s[0]) - 1;
-  const int32_t by0 = __builtin_amdgcn_readfirstlane(win_s[1]) - 1;
-  const int32_t bw = __builtin_amdgcn_readfirstlane(win_s[2]) + 3 - bx0 + 1;
-  const int32_t bh = __builtin_amdgcn_readfirstlane(win_s[3]) + 3 - by0 + 1;
-  const int32_t xa = bx0 >= 0 ? (bx0 & ~3) : -((-bx0 + 3) & ~3);  // window start, dword aligned
-  const int nd = (bx0 - xa + bw + 3) >> 2;                         // source dwords per row
-  const bool staged = bw > 0 && bh > 0 && 4 * nd <= kRFS && bh <= max_rows;
+  // Source window of the tile's in-mask pixels (their 4x4 taps included) and
+  // the tile's class, from the record (rot_tile, rot_tiles.h)
+  const int32_t bx0 = T.bx0, by0 = T.by0, bw = T.bw, bh = T.bh;
+  const int32_t xa = rot_window_xa(bx0);    // window start, dword aligned
+  const int nd = rot_window_nd(bx0, bw);    // source dwords per row
+  // (bh <= max_rows restated: the LDS window is this launch's)
+  const bool staged = (T.flags & ROT_T_STAGED) && bh <= max_rows;
   uint64_t* nw = reinterpret_cast<uint64_t*>(winf + kRFS * max_rows);
   uint8_t* obuf = reinterpret_cast<uint8_t*>(nw + max_rows) + wu * (kRFH / kRFWaves * kRFW);
   if (staged && !UPH_DIAG_BITS(diag, 1024)) {
@@ -820,7 +849,7 @@ __global__ void __launch_bounds__(kRFT, UPH_ROT_MINB) k_rotate_cubic_g8f(PlaneRe
         d[1] = make_float4(ubyte_f<0>(w1), ubyte_f<1>(w1), ubyte_f<2>(w1), ubyte_f<3>(w1));
       }
     };
-    const bool interior = xa >= 0 && xa + 8 * nq <= P.W && by0 >= 0 && by0 + bh <= P.H;
+    const bool interior = T.flags & ROT_T_INTERIOR;
     if (interior) {
       // the whole window inside the image: straight loads.  A lane's byte
       // offset is its row-rq offset plus a scalar row product per group;
@@ -832,7 +861,8 @@ __global__ void __launch_bounds__(kRFT, UPH_ROT_MINB) k_rotate_cubic_g8f(PlaneRe
         for (int g = 0; g < 3; g++) {  // all loads of the group in flight
           const int rb = rg + 3 * kRFWaves * g;
           const uint32_t o = rb + rq < bh ? off0 + (uint32_t)rb * (uint32_t)P.pitch : off0;
-          v[g] = *reinterpret_cast<const uint2*>(sbase + o);
+          const uint64_t q = gload<uint64_t>(sbase + o);
+          v[g] = make_uint2((uint32_t)q, (uint32_t)(q >> 32));
         }
 #pragma unroll
         for (int g = 0; g < 3; g++) {
@@ -861,8 +891,8 @@ __global__ void __launch_bounds__(kRFT, UPH_ROT_MINB) k_rotate_cubic_g8f(PlaneRe
           const int r = rg + 3 * kRFWaves * g + rq;
           const int32_t y = imin(imax(by0 + r, 0), P.H - 1);
           const uint8_t* row = sbase + row_off(y, P.pitch);
-          v[g].x = *reinterpret_cast<const uint32_t*>(row + xc0);
-          v[g].y = *reinterpret_cast<const uint32_t*>(row + xc1);
+          v[g].x = gload<uint32_t>(row + xc0);
+          v[g].y = gload<uint32_t>(row + xc1);
         }
 #pragma unroll
         for (int g = 0; g < 3; g++) {
@@ -884,7 +914,7 @@ __global__ void __launch_bounds__(kRFT, UPH_ROT_MINB) k_rotate_cubic_g8f(PlaneRe
   // per-lane terms of the source coordinates (constant down the column):
   //   srcX = (scx + (u - tcx) cos) + (v - tcy) sin
   //   srcY = (scy + (v - tcy) cos) - (u - tcx) sin
-  const int32_t uA = xA - a.mask.x0, uB = xB - a.mask.x0;
+  const int32_t uA = xA - a.mx0, uB = xB - a.mx0;
   const float cuA = uA - tcx, cuB = uB - tcx;
   const float axA = scx + cuA * a.cosval, bsA = cuA * a.sinval;
   const float axB = scx + cuB * a.cosval, bsB = cuB * a.sinval;
@@ -897,7 +927,7 @@ __global__ void __launch_bounds__(kRFT, UPH_ROT_MINB) k_rotate_cubic_g8f(PlaneRe
   // with the same expressions, wave-uniform).  When every tap there is white
   // (255) the bicubic result is exactly 255: all differences are zero, so
   // each cubic_scale returns b + (+-0) = b.
-  const float cuL = (tx0 - a.mask.x0) - tcx, cuR = (tx0 + kRFW - 1 - a.mask.x0) - tcx;
+  const float cuL = (tx0 - a.mx0) - tcx, cuR = (tx0 + kRFW - 1 - a.mx0) - tcx;
   const float bsL = cuL * a.sinval, bsR = cuR * a.sinval;
   constexpr int kRows = kRFH / kRFWaves;            // rows per wave
   const int32_t yw = ty0 + wu * kRows;              // the wave's rows: yw .. yw + kRows-1
@@ -909,7 +939,7 @@ __global__ void __launch_bounds__(kRFT, UPH_ROT_MINB) k_rotate_cubic_g8f(PlaneRe
   // stores: lane -> row k0 + lane/16, bytes 8*(lane%16), k0 = 0, 4.
   const int cb = 8 * (lane & 15);
   const int32_t xo = tx0 + cb;
-  const bool partial = !(cu0 == u0 && cu1 == u1 && cv0 == v0 && cv1 == v1);
+  const bool partial = T.flags & ROT_T_PARTIAL;
   if (partial) {
     constexpr int kQ = (kRows + 3) / 4;
     uint64_t q[kQ];
@@ -919,7 +949,7 @@ __global__ void __launch_bounds__(kRFT, UPH_ROT_MINB) k_rotate_cubic_g8f(PlaneRe
       const int rr = 4 * h + (lane >> 4);
       const int32_t y = imin(yw + rr, P.H - 1);
       const int32_t x = imin(xo, (int32_t)P.pitch - 8);  // rows are 256-byte pitched
-      if (rr < kRows) q[h] = *reinterpret_cast<const uint64_t*>(sbase + row_off(y, P.pitch) + x);
+      if (rr < kRows) q[h] = gload<uint64_t>(sbase + row_off(y, P.pitch) + x);
     }
 #pragma unroll
     for (int h = 0; h < kQ; h++) {
@@ -942,7 +972,7 @@ __global__ void __launch_bounds__(kRFT, UPH_ROT_MINB) k_rotate_cubic_g8f(PlaneRe
       const int k = g + (lane >> 3), j = lane & 7;
       bool hit = false;
       if (k < kRows) {
-        const float cv = (yw + k - a.mask.y0) - tcy;
+        const float cv = (yw + k - a.my0) - tcy;
         const float VC = scy + cv * a.cosval;
         const int32_t yl = (int)(VC - bsL), yr = (int)(VC - bsR);
         const int32_t r0 = imax(imin(yl, yr) - 1 - by0, 0);
@@ -960,7 +990,7 @@ __global__ void __launch_bounds__(kRFT, UPH_ROT_MINB) k_rotate_cubic_g8f(PlaneRe
   // Every source coordinate of the tile's in-mask pixels is >= 1 when the
   // window starts inside the image: then (int)c == floor(c) and
   // c - (int)c == fract(c) exactly (one instruction instead of three).
-  const bool posc = bx0 >= 0 && by0 >= 0;
+  const bool posc = T.flags & ROT_T_POSC;
   // LDS byte address of window (row 0, column 0) minus the 4x4 tap offset,
   // so a pixel's first tap sits at wbase + 4 (iy kRFS + ix)
   const uint32_t wbase = lds0 - 4u * (uint32_t)((1 + by0) * kRFS + 1 + xa);
@@ -974,7 +1004,7 @@ __global__ void __launch_bounds__(kRFT, UPH_ROT_MINB) k_rotate_cubic_g8f(PlaneRe
 #pragma unroll
   for (int k = 0; k < kRows; k++) {
     const int32_t y = yw + k;
-    const int32_t v = y - a.mask.y0;
+    const int32_t v = y - a.my0;
     const bool rowin = FULL || ((v >= 0) & (v < sh) & (y < P.H));
     const float cv = v - tcy;
     const float VS = cv * a.sinval, VC = scy + cv * a.cosval;
@@ -1052,8 +1082,7 @@ __global__ void __launch_bounds__(kRFT, UPH_ROT_MINB) k_rotate_cubic_g8f(PlaneRe
     }
   }
   };
-  const bool full =
-      !partial && staged && posc && tx0 + kRFW <= P.W && ty0 + kRFH <= P.H;
+  const bool full = (T.flags & ROT_T_FULL) && staged;
   if (full)
     row_loop(std::true_type{});
   else
@@ -1064,7 +1093,7 @@ __global__ void __launch_bounds__(kRFT, UPH_ROT_MINB) k_rotate_cubic_g8f(PlaneRe
 #pragma unroll 1
     for (int k = 0; k < kRows; k++) {
       const int32_t y = yw + k;
-      const int32_t v = y - a.mask.y0;
+      const int32_t v = y - a.my0;
       const bool rowin = (v >= 0) & (v < sh) & (y < P.H);
       const float cv = v - tcy;
       const float VS = cv * a.sinval, VC = scy + cv * a.cosval;
@@ -1084,7 +1113,7 @@ __global__ void __launch_bounds__(kRFT, UPH_ROT_MINB) k_rotate_cubic_g8f(PlaneRe
       const int rr = k0 + (lane >> 4);
       if (rr < kRows) {
         const uint64_t q = *reinterpret_cast<const uint64_t*>(obuf + rr * kRFW + cb);
-        *reinterpret_cast<uint64_t*>(dbase + row_off(yw + rr, P.pitch) + xo) = q;
+        gstore<uint64_t>(dbase + row_off(yw + rr, P.pitch) + xo, q);
       }
     }
   } else
@@ -1095,9 +1124,9 @@ __global__ void __launch_bounds__(kRFT, UPH_ROT_MINB) k_rotate_cubic_g8f(PlaneRe
       const uint64_t q = *reinterpret_cast<const uint64_t*>(obuf + rr * kRFW + cb);
       uint8_t* d = dbase + row_off(y, P.pitch) + x;
       if (x + 8 <= P.W) {
-        *reinterpret_cast<uint64_t*>(d) = q;
+        gstore<uint64_t>(d, q);
       } else {
-        for (int j = 0; x + j < P.W; j++) d[j] = (uint8_t)(q >> (8 * j));
+        for (int j = 0; x + j < P.W; j++) gstore<uint8_t>(d + j, (uint8_t)(q >> (8 * j)));
       }
     }
   }
@@ -1124,20 +1153,20 @@ __global__ void __launch_bounds__(kRFT, UPH_ROT_MINB) k_rotate_cubic_g8f(PlaneRe
 #endif
   };
   if constexpr (!LOOP) {  // one tile per block, XCD-aware order
-    int txi, tyi, s;
-    xcd_block_m(m_gxy, m_gx, &txi, &tyi, &s);
-    tile(txi, tyi, s);
+    int txi, tyi, s, ti;
+    xcd_block_m(m_gxy, m_gx, &txi, &tyi, &s, &ti);
+    tile(txi, tyi, s, ti);
   } else {
-  // Persistent form for the large-window class, usually empty: the lanes of
-  // every wave test 64 sheets at once (the same ballot in every wave), and
-  // the block walks the tiles of the sheets that belong here.
+  // Persistent form for the large-window class, usually empty: then the
+  // launch's count of large-window sheets is 0 and every block ends after
+  // that one load.  Otherwise the lanes of every wave test 64 sheets at once
+  // (the same ballot in every wave), and the block walks the tiles of the
+  // sheets that belong here.
+  if (*nlarge == 0) return;
   for (int s0 = 0; s0 < loop_count; s0 += 64) {
     const int l = threadIdx.x & 63;
     bool want = false;
-    if (s0 + l < loop_count) {
-      const RotateArgs q = args[s0 + l];
-      want = q.active && kRFH + (int)ceilf((kRFW - 1) * fabsf(q.sinval)) + 5 > -cls_rows;
-    }
+    if (s0 + l < loop_count) want = sheets[s0 + l].active && sheets[s0 + l].large;
     uint64_t m = __ballot(want);
     m = ((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(m >> 32)) << 32) |
         __builtin_amdgcn_readfirstlane((uint32_t)m);
@@ -1145,7 +1174,7 @@ __global__ void __launch_bounds__(kRFT, UPH_ROT_MINB) k_rotate_cubic_g8f(PlaneRe
       const int s = s0 + __ffsll((long long)m) - 1;
       m &= m - 1;
       for (int t = blockIdx.x; t < tgx * tgy; t += gridDim.x) {
-        tile(t % tgx, t / tgx, s);
+        tile(t % tgx, t / tgx, s, s * (tgx * tgy) + t);
         __syncthreads();  // the next tile restages the LDS window
       }
     }
@@ -1161,9 +1190,19 @@ static int rotate_window_rows(float max_abs_angle) {
   return kRFH + (int)ceilf((kRFW - 1) * sinf(a)) + 5;
 }
 
+// k_rot_tiles' records of one launch: the count of large-window sheets (its
+// own 64 bytes), the RotSheet of every sheet, then every sheet's RotTile.
+static size_t rot_tiles_per_sheet(int32_t W, int32_t H) {
+  return (size_t)((W + kRFW - 1) / kRFW) * (size_t)((H + kRFH - 1) / kRFH);
+}
+size_t rotate_scratch_bytes(int32_t W, int32_t H, int count) {
+  return 64 + (sizeof(RotSheet) + sizeof(RotTile) * rot_tiles_per_sheet(W, H)) * (size_t)count;
+}
+static_assert(sizeof(RotSheet) == 64 && sizeof(RotTile) == 16, "records are read as whole dwords");
+
 bool launch_rotate_mask(const PlaneRef& src, const PlaneRef& dst, const RotateArgs* args,
                         int interp, int count, hipStream_t st, float max_abs_angle,
-                        uint32_t* colsum, int64_t cs_stride) {
+                        void* scratch, uint32_t* colsum, int64_t cs_stride) {
   const dim3 grid((src.P.W + kRotTW - 1) / kRotTW, (src.P.H + kRotTH - 1) / kRotTH, count);
   const dim3 ggrid((src.P.W + kRotTW - 1) / kRotTW, (src.P.H + kRotGH - 1) / kRotGH, count);
   if (interp == UPHIP_INTERP_CUBIC && src.P.fmt == F_GRAY8) {
@@ -1173,7 +1212,8 @@ bool launch_rotate_mask(const PlaneRef& src, const PlaneRef& dst, const RotateAr
       return (sizeof(float) * kRFS + sizeof(uint64_t)) * (size_t)r + kRFH * kRFW;
     };
     // the most window rows that still let four tiles (32 waves) share a CU's
-    // 160 KB of LDS (16 + 512 B of static LDS per tile); windows of up to ~2.4 deg
+    // 160 KB of LDS (512 B of static LDS per tile; the 16 B more that the
+    // bound still allows were the window bounds'); windows of up to ~2.25 deg
     const int rows4 = (int)((40 * 1024 - 16 - 4 * kRFW - kRFH * kRFW) /
                             (sizeof(float) * kRFS + sizeof(uint64_t)));
     if (lds_of(rows) <= 56 * 1024 &&
@@ -1193,27 +1233,37 @@ bool launch_rotate_mask(const PlaneRef& src, const PlaneRef& dst, const RotateAr
           hipMemcpyToSymbol(HIP_SYMBOL(g_rot_phase), z, sizeof(z));
           for (int i = 0; i < 1024 * 8; i++) h[i & 7] += hh[i];
           if (!h[7]) return;
-          fprintf(stderr, "rotate phases (10 ns ticks/tile, %llu tiles): args %.0f corners %.0f staging %.0f "
+          fprintf(stderr, "rotate phases (10 ns ticks/tile, %llu tiles): index %.0f records %.0f staging %.0f "
                   "flags %.0f compute %.0f stores %.0f colsum %.0f\n", h[7], (double)h[0] / h[7],
                   (double)h[1] / h[7], (double)h[2] / h[7], (double)h[3] / h[7],
                   (double)h[4] / h[7], (double)h[5] / h[7], (double)h[6] / h[7]);
         }
       } phase_print{st};
 #endif
-      if (rows > rows4) {
+      // the records of this launch (k_rot_tiles), then the tiles that read them
+      uint32_t* nlarge = static_cast<uint32_t*>(scratch);
+      RotSheet* sheets = reinterpret_cast<RotSheet*>(static_cast<uint8_t*>(scratch) + 64);
+      RotTile* tiles = reinterpret_cast<RotTile*>(sheets + count);
+      const RotPlane rp{src.P.W, src.P.H, (uint32_t)src.P.pitch};
+      const int tgx = (int)fgrid.x, tgy = (int)fgrid.y;
+      const bool split = rows > rows4;
+      hipLaunchKernelGGL(k_rot_tiles, dim3((tgx * tgy + 255) / 256, count), dim3(256), 0, st, src,
+                         dst, args, count, tgx, tgy, split ? rows4 : rows, rows, split ? rows4 : 0,
+                         sheets, tiles, nlarge);
+      if (split) {
         // sheets whose angle fits the small window at four tiles per CU, then
         // the others at the scan range's window (three per CU); every sheet
         // is taken by exactly one of the two launches
         // (the second as a persistent grid: when no sheet needs the large
-        // window its blocks only read the arguments)
-        UPH_LAUNCH_DIAG(2, k_rotate_cubic_g8f<false>, fgrid, dim3(kRFT), lds_of(rows4), st, src, dst, args,
-                        rows4, rows4, dd, mgxy, mgx, 0, 0, 0, colsum, cs_stride);
-        UPH_LAUNCH_DIAG(2, k_rotate_cubic_g8f<true>, dim3(3 * 256), dim3(kRFT), lds_of(rows), st, src, dst,
-                        args, rows, -rows4, dd, 0u, 0u, count, (int)fgrid.x, (int)fgrid.y, colsum,
+        // window its blocks only read the launch's count of such sheets)
+        UPH_LAUNCH_DIAG(2, k_rotate_cubic_g8f<false>, fgrid, dim3(kRFT), lds_of(rows4), st, sheets,
+                        tiles, nlarge, rp, rows4, dd, mgxy, mgx, 0, 0, 0, colsum, cs_stride);
+        UPH_LAUNCH_DIAG(2, k_rotate_cubic_g8f<true>, dim3(3 * 256), dim3(kRFT), lds_of(rows), st,
+                        sheets, tiles, nlarge, rp, rows, dd, 0u, 0u, count, tgx, tgy, colsum,
                         cs_stride);
       } else {
-        UPH_LAUNCH_DIAG(2, k_rotate_cubic_g8f<false>, fgrid, dim3(kRFT), lds_of(rows), st, src, dst, args,
-                        rows, 0, dd, mgxy, mgx, 0, 0, 0, colsum, cs_stride);
+        UPH_LAUNCH_DIAG(2, k_rotate_cubic_g8f<false>, fgrid, dim3(kRFT), lds_of(rows), st, sheets,
+                        tiles, nlarge, rp, rows, dd, mgxy, mgx, 0, 0, 0, colsum, cs_stride);
       }
       return colsum != nullptr;
     }

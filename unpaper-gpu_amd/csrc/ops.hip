@@ -540,10 +540,11 @@ void uphip_deskew(UphipImage source0, UphipRectangle mask, float radians,
   UphipFrame* n = frame_alloc(f->width, f->height, f->format);
   if (!n) return;
   RotateArgs* d = stage_args(&a, 1, st);
-  if (!d) return;
+  void* rs = scratch(0, rotate_scratch_bytes(f->width, f->height, 1));  // stream-ordered
+  if (!d || !rs) return;
   if (!(interp == UPHIP_INTERP_LINEAR &&
         launch_rotate_linear(ref_of(f), ref_of(n), d, 1, 1, nullptr, 1, st, radians)))
-    launch_rotate_mask(ref_of(f), ref_of(n), d, interp, 1, st, radians);
+    launch_rotate_mask(ref_of(f), ref_of(n), d, interp, 1, st, radians, rs);
   arg_fence(st);
   adopt_storage(f, n);
   mp.finish();

@@ -446,6 +446,7 @@ struct UphipBatch {
   Rect* pick_mask = nullptr;
   int32_t* pick_active = nullptr;
   RotateArgs* rot_args = nullptr;      // [UPHIP_MAX_PAGES][cap]
+  uint8_t* rot_scratch = nullptr;      // launch_rotate_mask's records (one launch at a time: stream-ordered)
   int32_t* rot_indep = nullptr;        // two-mask launch: mask 1 independent of deskew 0
   int32_t* rot_dep = nullptr;          // ... or redone after it
   uint32_t* nbits = nullptr;           // GRAY8 noisefilter dark bit-plane (k_decode_gray)
@@ -779,6 +780,8 @@ static bool allocate(UphipBatch* b) {
   b->border_need = dalloc<int32_t>(b, cap);
   b->border_mask_args = dalloc<MaskArgs>(b, cap);
   b->rot_args = dalloc<RotateArgs>(b, (size_t)cap * UPHIP_MAX_PAGES);
+  b->rot_scratch = dalloc<uint8_t>(b, rotate_scratch_bytes(b->max_w, b->max_h, cap));
+  if (!b->rot_scratch) return false;
   b->rot_indep = dalloc<int32_t>(b, cap);
   b->rot_dep = dalloc<int32_t>(b, cap);
   b->pick_mask = dalloc<Rect>(b, cap);
@@ -1403,8 +1406,8 @@ static bool run_batch(UphipBatch* b, int count, const uint8_t* src, int64_t spit
                                          b->cap, indep, count, b->st, b->max_angle))
         return false;
       return launch_rotate_mask(cur_ref(P, b->ctl), other_ref(P, b->ctl), args,
-                                o.interpolate_type, count, b->st, b->max_angle, colsum,
-                                b->sums_stride);
+                                o.interpolate_type, count, b->st, b->max_angle, b->rot_scratch,
+                                colsum, b->sums_stride);
     };
     if (linear && b->points.size() == 2) {
       // both masks detected on the same image, rotated in one launch where
