@@ -467,6 +467,22 @@ int64_t uphip_batch_jpeg_sizes(UphipBatch *batch, int64_t *sizes, int32_t max_pa
 int uphip_batch_jpeg_download_async(UphipBatch *batch, void *host, int64_t capacity);
 int uphip_batch_jpeg_page(UphipBatch *batch, int32_t page, const void **device_src,
                           int64_t *pitch, int32_t *width, int32_t *height, int32_t *format);
+/* The bilevel output branch for a whole batch, the peer of the three JPEG
+ * calls above for batches whose output format is MONOWHITE (any other format
+ * fails): queued on the batch stream after uphip_batch_run*, it encodes
+ * every output page of the last run (page j of a sheet starts at bit
+ * j * (width / output_count) of the sheet's packed rows) as a CCITT Group 4
+ * stream (uphip_g4_encode) and packs the streams one after another in device
+ * memory, then copies their sizes to the host.  After the stream is idle:
+ *   g4_sizes:           sizes[i] of page i (-1: larger than its share of the
+ *                       encode buffer, the page's packed bytes + 1 KiB:
+ *                       re-encode it with uphip_g4_encode from
+ *                       uphip_batch_output_ptr); returns the packed total
+ *   g4_download_async:  the packed streams into host memory (total bytes).
+ * The encode buffers are allocated by the first encode. */
+int uphip_batch_encode_g4_async(UphipBatch *batch);
+int64_t uphip_batch_g4_sizes(UphipBatch *batch, int64_t *sizes, int32_t max_pages);
+int uphip_batch_g4_download_async(UphipBatch *batch, void *host, int64_t capacity);
 /* Row pitch of the output sheets on the device: host staging with this
  * linesize (and pitch * height per sheet) downloads as linear DMA copies. */
 int uphip_batch_output_pitch(UphipBatch *batch, int64_t *pitch);
@@ -573,6 +589,28 @@ int64_t uphip_jp2_entropy_decode(const void *data, size_t size, void *coef, int6
  * Synchronous; -1 on error. */
 int64_t uphip_jp2_encode(const void *device_src, int64_t pitch, int32_t width,
                          int32_t height, int32_t format, void *out, int64_t capacity);
+/* CCITT Group 4 (ITU-T T.6) encode of a bilevel image, the format of scanned
+ * pages in TIFF (Compression 4) and PDF (/CCITTFaxDecode, /K -1): packed
+ * rows, MSB first, 1 = black (MONOWHITE), pixel 0 of a row at bit
+ * `bit_offset` of it; bits outside [bit_offset, bit_offset + width) are not
+ * read as pixels.  The stream has no header: rows coded one after another
+ * against the row above (the first against a white row), EOFB, zero padding
+ * to a byte.  The bytes equal libtiff's for the same pixels.  Returns the
+ * stream's size; the bytes are copied to `out` (host memory) only when
+ * `capacity` suffices (out = NULL sizes a buffer); -1 on error.
+ *   uphip_g4_encode_host: rows `stride` apart in host memory; needs no device.
+ *   uphip_g4_encode:      rows `pitch` apart in device memory, coded on the
+ *                         current device (a lane per row: a count pass, a
+ *                         prefix sum, an emit pass into a buffer of the
+ *                         exact size); synchronous. */
+int64_t uphip_g4_encode_host(const void *bits, int64_t stride, int32_t bit_offset,
+                             int32_t width, int32_t height, void *out, int64_t capacity);
+int64_t uphip_g4_encode(const void *device_src, int64_t pitch, int32_t bit_offset,
+                        int32_t width, int32_t height, void *out, int64_t capacity);
+/* A Group 4 stream as a TIFF file, the container uphip_sink_tiff_g4 writes:
+ * classic, little-endian, one strip; dpi 0 = 300.  0 / -1. */
+int uphip_tiff_g4_write(const char *path, const uint8_t *data, size_t len, int32_t width,
+                        int32_t height, int32_t dpi);
 /* Any codec, picked by the file's signature (PNG, JPEG, JPEG 2000 or PNM). */
 int uphip_image_probe(const char *path, UphipPnmInfo *info);
 int uphip_image_read(const char *path, void *dst, int64_t linesize,
@@ -663,6 +701,13 @@ int uphip_pdf_writer_add_page_jp2(UphipPdfWriter *writer, const uint8_t *data, s
 int uphip_pdf_writer_add_page_pixels(UphipPdfWriter *writer, const uint8_t *pixels,
                                      int32_t width, int32_t height, int32_t stride,
                                      int32_t format, int32_t dpi);
+/* A bilevel page from its Group 4 stream (uphip_g4_encode*, 1 = black): an
+ * image with /Filter /CCITTFaxDecode, /DecodeParms << /K -1 /Columns width
+ * /Rows height /BlackIs1 true >>, /BitsPerComponent 1 and /DeviceGray.
+ * /BlackIs1 makes the decoded black pixels 1-bits, as in the source rows, so
+ * the image also carries /Decode [1 0]: 1 paints black. */
+int uphip_pdf_writer_add_page_g4(UphipPdfWriter *writer, const uint8_t *data, size_t len,
+                                 int32_t width, int32_t height, int32_t dpi);
 int uphip_pdf_writer_page_count(UphipPdfWriter *writer);
 /* lib/jbig2_decode.h:19-45 (jbig2_decode over jbig2dec): an embedded JBIG2
  * stream (+ its globals) to a 1-bit page, MSB first, 1 = black, rows
@@ -773,6 +818,21 @@ UphipSource *uphip_source_pdf(const char *path, int32_t dpi);
 int64_t uphip_source_page_count(UphipSource *source);
 UphipSink *uphip_sink_pdf(const char *path, const UphipPdfMetadata *meta, int32_t dpi,
                           int32_t quality, int32_t mode);
+/* Bilevel documents: for runners whose sheets leave as MONOWHITE (a bilevel
+ * output_pixel_format, or bilevel pages with none set; uphip_runner_run_host
+ * refuses any other before it starts, naming output_pixel_format).  The pages are coded as CCITT Group 4 on the device
+ * right after their batch (uphip_batch_encode_g4_async) and only the streams
+ * cross PCIe.
+ *   uphip_sink_tiff_g4:     one classic little-endian TIFF per output page
+ *                           (one strip, RowsPerStrip = height, Compression 4,
+ *                           Photometric 0 = min-is-white, FillOrder 1,
+ *                           T6Options 0, resolution `dpi` per inch, 0 = 300);
+ *                           names as uphip_sink_pnm.
+ *   uphip_sink_pdf_bilevel: one PDF of Group 4 pages
+ *                           (uphip_pdf_writer_add_page_g4); ordering, skipped
+ *                           pages, dpi, finish and destroy as uphip_sink_pdf. */
+UphipSink *uphip_sink_tiff_g4(const char *pattern, int64_t wrap, int32_t dpi);
+UphipSink *uphip_sink_pdf_bilevel(const char *path, const UphipPdfMetadata *meta, int32_t dpi);
 int uphip_sink_finish(UphipSink *sink);
 void uphip_sink_destroy(UphipSink *sink);
 

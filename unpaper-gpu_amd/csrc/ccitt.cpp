@@ -1,10 +1,13 @@
-// CCITT fax decoding (ITU-T T.4 / T.6) of PDF /CCITTFaxDecode images (ccitt.h).
+// CCITT fax decoding (ITU-T T.4 / T.6) of PDF /CCITTFaxDecode images and the
+// host Group 4 encoder (ccitt.h).
 #include "ccitt.h"
 
 #include <algorithm>
 #include <cstring>
 
+#include "g4_row.h"
 #include "runtime.h"
+#include "unpaper_hip.h"
 
 namespace uph {
 namespace ccitt {
@@ -259,5 +262,77 @@ bool decode(const uint8_t* data, size_t n, const Params& prm, int32_t rows, Imag
   return true;
 }
 
+namespace {
+
+// A row of a host bitmap for g4_row.h: bytes past the row's pixels read as
+// zeros (never past the caller's buffer); p = nullptr is an all-white row.
+struct HostRow {
+  const uint8_t* p;  // the byte that holds pixel 0
+  int64_t nbytes;    // bytes that hold pixels
+  int off;           // bit of p[0] that is pixel 0
+  uint32_t word(int i) const {
+    uint32_t v = 0;
+    for (int k = 0; k < 4; k++) {
+      const int64_t at = (int64_t)i * 4 + k;
+      v = v << 8 | (p && at < nbytes ? p[at] : 0u);
+    }
+    return v;
+  }
+};
+
+struct AppendSink {
+  std::vector<uint8_t>* out;
+  uint64_t acc = 0;  // pending bits, left-aligned
+  int n = 0;
+  void put(uint32_t code, int len) {
+    acc |= (uint64_t)code << (64 - n - len);
+    n += len;
+    while (n >= 8) {
+      out->push_back((uint8_t)(acc >> 56));
+      acc <<= 8;
+      n -= 8;
+    }
+  }
+  void flush() {  // zero padding to a byte
+    if (n > 0) out->push_back((uint8_t)(acc >> 56));
+    acc = 0;
+    n = 0;
+  }
+};
+
+}  // namespace
+
+bool encode(const uint8_t* bits, int64_t stride, int32_t bit_offset, int32_t width, int32_t height,
+            std::vector<uint8_t>* out) {
+  if (!bits || !out) return fail("g4_encode: null argument");
+  if (width <= 0 || width > (1 << 20) || height <= 0 || height > (1 << 20))
+    return fail("g4_encode: invalid size %dx%d", width, height);
+  if (bit_offset < 0 || (int64_t)bit_offset + width > stride * 8)
+    return fail("g4_encode: bits %d..%lld do not fit rows of %lld bytes", bit_offset,
+                (long long)bit_offset + width, (long long)stride);
+  out->clear();
+  AppendSink sink{out};
+  const int off = bit_offset & 7;
+  const int64_t nbytes = ((int64_t)off + width + 7) / 8;
+  HostRow ref{nullptr, 0, off};
+  for (int32_t y = 0; y < height; y++) {
+    const HostRow cur{bits + (int64_t)y * stride + (bit_offset >> 3), nbytes, off};
+    g4::encode_row(cur, ref, width, g4::kRun, sink);
+    ref = cur;
+  }
+  sink.put(g4::kEol, g4::kEolBits);
+  sink.put(g4::kEol, g4::kEolBits);
+  sink.flush();
+  return true;
+}
+
 }  // namespace ccitt
 }  // namespace uph
+
+extern "C" int64_t uphip_g4_encode_host(const void* bits, int64_t stride, int32_t bit_offset, int32_t width,
+                                        int32_t height, void* out, int64_t capacity) {
+  std::vector<uint8_t> s;
+  if (!uph::ccitt::encode((const uint8_t*)bits, stride, bit_offset, width, height, &s)) return -1;
+  if (out && capacity >= (int64_t)s.size()) memcpy(out, s.data(), s.size());
+  return (int64_t)s.size();
+}

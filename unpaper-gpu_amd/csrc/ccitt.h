@@ -31,5 +31,14 @@ struct Image {
 // Decodes `rows` rows (rows the data does not reach stay white).
 bool decode(const uint8_t* data, size_t n, const Params& prm, int32_t rows, Image* out, const char* name);
 
+// Group 4 (T.6) encode of a bitmap, the coder of g4_row.h row by row: rows
+// `stride` bytes apart, MSB first, 1 = black, pixel 0 of a row at bit
+// `bit_offset` of it; bits outside [bit_offset, bit_offset + width) are not
+// read as pixels.  The stream ends with EOFB, padded to a byte: the strip a
+// TIFF (Compression 4) or a PDF (/CCITTFaxDecode, /K -1) holds, and what the
+// device encoder (kernels_g4.hip) must equal.
+bool encode(const uint8_t* bits, int64_t stride, int32_t bit_offset, int32_t width, int32_t height,
+            std::vector<uint8_t>* out);
+
 }  // namespace ccitt
 }  // namespace uph

@@ -1628,6 +1628,8 @@ bool Writer::add_page(int64_t index, int kind, const uint8_t* data, size_t len, 
   const uint8_t* body = data;
   size_t blen = len;
   const char* filter = nullptr;
+  int bpc = 8;
+  char parms[160] = "";
   if (kind == kJpeg) {
     filter = "DCTDecode";
     const int c = jpeg_components(data, len);
@@ -1641,6 +1643,14 @@ bool Writer::add_page(int64_t index, int kind, const uint8_t* data, size_t len, 
       uphip_clear_error();
       components = 3;  // pdf_writer.c:339-341
     }
+  } else if (kind == kCcitt) {
+    // a Group 4 stream whose black runs are black pixels (ccitt::encode):
+    // /BlackIs1 makes them 1-bits and /Decode [1 0] paints 1 black
+    filter = "CCITTFaxDecode";
+    components = 1;
+    bpc = 1;
+    snprintf(parms, sizeof(parms), " /DecodeParms << /K -1 /Columns %d /Rows %d /BlackIs1 true >> /Decode [1 0]",
+             width, height);
   } else if (kind == kRaw) {
     if (components != 1 && components != 3) return fail("pdf_writer: pixels must have 1 or 3 components");
     const size_t rb = (size_t)width * components;
@@ -1666,7 +1676,7 @@ bool Writer::add_page(int64_t index, int kind, const uint8_t* data, size_t len, 
   const std::string spw = real(pw), sph = real(ph);
   char content[160];
   const int cl = snprintf(content, sizeof(content), "q %s 0 0 %s 0 0 cm /Im0 Do Q", spw.c_str(), sph.c_str());
-  char h1[320], t1[640];
+  char h1[480], t1[640];
   int64_t off;
   int n1, n2;
   {
@@ -1676,9 +1686,9 @@ bool Writer::add_page(int64_t index, int kind, const uint8_t* data, size_t len, 
     if (failed_) return false;
     const int64_t im = (int64_t)offsets_.size(), ct = im + 1, pg = im + 2;
     n1 = snprintf(h1, sizeof(h1),
-                  "%lld 0 obj\n<< /Type /XObject /Subtype /Image /Width %d /Height %d /BitsPerComponent 8 "
-                  "/ColorSpace %s /Filter /%s /Length %zu >>\nstream\n",
-                  (long long)im, width, height, cs, filter, blen);
+                  "%lld 0 obj\n<< /Type /XObject /Subtype /Image /Width %d /Height %d /BitsPerComponent %d "
+                  "/ColorSpace %s /Filter /%s%s /Length %zu >>\nstream\n",
+                  (long long)im, width, height, bpc, cs, filter, parms, blen);
     const int a = snprintf(t1, sizeof(t1), "\nendstream\nendobj\n%lld 0 obj\n<< /Length %d >>\nstream\n%s\nendstream\nendobj\n",
                            (long long)ct, cl, content);
     const int b = snprintf(t1 + a, sizeof(t1) - (size_t)a,
@@ -2033,6 +2043,12 @@ int uphip_pdf_writer_add_page_jp2(UphipPdfWriter* w, const uint8_t* data, size_t
                                   int32_t height, int32_t dpi) {
   if (!w) return fail("pdf_writer: Invalid arguments"), -1;
   return w->w.add_page_next(uph::pdf::kJp2, data, len, width, height, 0, 0, dpi) ? 0 : -1;
+}
+
+int uphip_pdf_writer_add_page_g4(UphipPdfWriter* w, const uint8_t* data, size_t len, int32_t width,
+                                 int32_t height, int32_t dpi) {
+  if (!w) return fail("pdf_writer: Invalid arguments"), -1;
+  return w->w.add_page_next(uph::pdf::kCcitt, data, len, width, height, 0, 0, dpi) ? 0 : -1;
 }
 
 int uphip_pdf_writer_add_page_pixels(UphipPdfWriter* w, const uint8_t* pixels, int32_t width, int32_t height,

@@ -176,7 +176,8 @@ class Writer {
  public:
   ~Writer();
   bool create(const char* path, const Meta* meta, int dpi);
-  // kind: kJpeg, kJp2 or kRaw (pixels: components 1 or 3, `stride` apart)
+  // kind: kJpeg, kJp2, kCcitt (a Group 4 stream, 1 = black: ccitt::encode) or
+  // kRaw (pixels: components 1 or 3, `stride` apart)
   bool add_page(int64_t index, int kind, const uint8_t* data, size_t len, int width, int height,
                 int stride, int components, int dpi);
   bool add_page_next(int kind, const uint8_t* data, size_t len, int width, int height, int stride,

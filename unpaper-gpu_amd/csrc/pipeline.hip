@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "filters.h"
+#include "g4_enc.h"
 #include "jpeg_enc.h"
 #include "libm_glibc.h"
 #include "runtime.h"
@@ -472,6 +473,9 @@ struct UphipBatch {
   // GPU JPEG output branch (uphip_batch_encode_jpeg_async)
   JencContext* jenc = nullptr;
   int jenc_pages = 0;
+  // bilevel output branch (uphip_batch_encode_g4_async)
+  G4Context* g4 = nullptr;
+  int g4_pages = 0;
 };
 
 namespace {
@@ -1577,6 +1581,7 @@ void uphip_batch_destroy(UphipBatch* b) {
     for (auto& m : r) hipEventDestroy(m.second);
   for (void* p : b->allocs) hipFree(p);
   delete b->jenc;
+  delete b->g4;
   if (b->st) hipStreamDestroy(b->st);
   delete b;
 }
@@ -1847,6 +1852,47 @@ int uphip_batch_jpeg_page(UphipBatch* b, int32_t page, const void** device_src, 
   if (height) *height = b->out_h;
   if (format) *format = b->work_fmt == F_GRAY8 ? UPHIP_FMT_GRAY8 : UPHIP_FMT_RGB24;
   return 0;
+}
+
+// ---- bilevel output branch: CCITT Group 4 (g4_enc.h) ----------------------
+int uphip_batch_encode_g4_async(UphipBatch* b) {
+  if (!b || b->last_count <= 0) return fail("batch_encode_g4: nothing to encode"), -1;
+  if (b->out_fmt != F_MONOWHITE || !b->out)
+    return fail("batch_encode_g4: the batch's output format is %d, Group 4 codes bilevel (MONOWHITE) "
+                "sheets only", b->out_fmt), -1;
+  hipSetDevice(b->device);
+  const int oc = b->o.output_count < 1 ? 1 : b->o.output_count;
+  const int32_t pw = b->out_w / oc;
+  if (pw <= 0) return fail("batch_encode_g4: empty pages"), -1;
+  // a page's share of the packed buffer: its packed rows + 1 KiB (text codes
+  // to a small fraction; a noisy page above it comes back as -1)
+  const int64_t share = row_bytes(pw, F_MONOWHITE) * b->out_h + 1024;
+  if (!b->g4) b->g4 = new G4Context();
+  const G4Pages pg{b->out, b->out_stride, b->out_pitch, oc, 0, pw, b->out_h, b->last_count * oc};
+  if (!b->g4->encode_async(pg, share, b->st)) return -1;
+  b->g4_pages = pg.npages;
+  return 0;
+}
+
+int64_t uphip_batch_g4_sizes(UphipBatch* b, int64_t* sizes, int32_t max_pages) {
+  if (!b || !b->g4 || b->g4_pages <= 0) return fail("batch_g4_sizes: no encode"), -1;
+  if (uphip_batch_query(b) != 1) return fail("batch_g4_sizes: the encode has not finished"), -1;
+  int64_t total = 0;
+  for (int i = 0; i < b->g4_pages; i++) {
+    const int64_t s = b->g4->host_sizes[i];
+    if (sizes && i < max_pages) sizes[i] = s < 0 ? -1 : s;
+    if (s > 0) total += s;
+  }
+  return total;
+}
+
+int uphip_batch_g4_download_async(UphipBatch* b, void* host, int64_t capacity) {
+  const int64_t total = uphip_batch_g4_sizes(b, nullptr, 0);
+  if (total < 0) return -1;
+  if (total == 0) return 0;  // every page came back -1
+  if (!host || capacity < total) return fail("batch_g4_download: buffer too small"), -1;
+  hipSetDevice(b->device);
+  return UPH_HIP(hipMemcpyAsync(host, b->g4->out, (size_t)total, hipMemcpyDeviceToHost, b->st)) ? 0 : -1;
 }
 
 int uphip_batch_set_timing(UphipBatch* b, int32_t enable) {

@@ -245,8 +245,11 @@ struct UphipSink {
   // lossless JPEG 2000 files (uphip_sink_jp2): transforms on the device from
   // the batch's output planes, code-blocks on the store tasks
   bool jp2 = false;
-  // one PDF of all the output pages (uphip_sink_pdf): the encoded pages go
-  // to the writer instead of files
+  // CCITT Group 4 streams coded on the device from bilevel sheets
+  // (uphip_sink_tiff_g4: a TIFF per page, at pdf_dpi; uphip_sink_pdf_bilevel)
+  bool g4 = false;
+  // one PDF of all the output pages (uphip_sink_pdf, uphip_sink_pdf_bilevel):
+  // the encoded pages go to the writer instead of files
   std::unique_ptr<uph::pdf::Writer> pdfw;
   int32_t pdf_dpi = 300;
   HostRegistration reg;
@@ -314,6 +317,58 @@ bool output_pattern(const char* p, std::string* out) {
     c = q;
   }
   return true;
+}
+
+// A Group 4 stream of a w x h page as a classic little-endian TIFF: header,
+// one IFD, the two resolution rationals, then the stream as the only strip.
+bool write_tiff_g4(const std::string& path, const uint8_t* p, size_t n, int32_t w, int32_t h, int32_t dpi) {
+  constexpr int kEntries = 14;
+  constexpr uint32_t kIfd = 8, kRes = kIfd + 2 + kEntries * 12 + 4, kStrip = kRes + 16;
+  if (n > 0xFFFFFFFFu - kStrip) return fail("tiff_g4: a %zu-byte strip does not fit a classic TIFF", n);
+  std::vector<uint8_t> f;
+  f.reserve(kStrip + n);
+  auto u16 = [&f](uint32_t v) {
+    f.push_back((uint8_t)v);
+    f.push_back((uint8_t)(v >> 8));
+  };
+  auto u32 = [&](uint32_t v) {
+    u16(v & 0xFFFF);
+    u16(v >> 16);
+  };
+  auto entry = [&](uint32_t tag, uint32_t type, uint32_t value) {  // type 3 SHORT, 4 LONG, 5 RATIONAL (offset)
+    u16(tag);
+    u16(type);
+    u32(1);
+    u32(value);  // a SHORT sits in the low half, the rest zero
+  };
+  u16(0x4949);
+  u16(42);
+  u32(kIfd);
+  u16(kEntries);
+  entry(256, 4, (uint32_t)w);        // ImageWidth
+  entry(257, 4, (uint32_t)h);        // ImageLength
+  entry(258, 3, 1);                  // BitsPerSample
+  entry(259, 3, 4);                  // Compression: CCITT T.6
+  entry(262, 3, 0);                  // PhotometricInterpretation: 0 is white
+  entry(266, 3, 1);                  // FillOrder: MSB first
+  entry(273, 4, kStrip);             // StripOffsets
+  entry(277, 3, 1);                  // SamplesPerPixel
+  entry(278, 4, (uint32_t)h);        // RowsPerStrip: one strip
+  entry(279, 4, (uint32_t)n);        // StripByteCounts
+  entry(282, 5, kRes);               // XResolution
+  entry(283, 5, kRes + 8);           // YResolution
+  entry(293, 4, 0);                  // T6Options
+  entry(296, 3, 2);                  // ResolutionUnit: inch
+  u32(0);                            // no further IFD
+  for (int i = 0; i < 2; i++) {
+    u32((uint32_t)dpi);
+    u32(1);
+  }
+  f.insert(f.end(), p, p + n);
+  FILE* o = fopen(path.c_str(), "wb");
+  if (!o) return fail("tiff_g4: cannot create %s", path.c_str());
+  const bool ok = fwrite(f.data(), 1, f.size(), o) == f.size();
+  return (fclose(o) == 0 && ok) || fail("tiff_g4: cannot write %s", path.c_str());
 }
 
 }  // namespace
@@ -462,6 +517,51 @@ UphipSink* uphip_sink_pdf(const char* path, const UphipPdfMetadata* meta, int32_
   return k;
 }
 
+UphipSink* uphip_sink_tiff_g4(const char* pattern, int64_t wrap, int32_t dpi) {
+  if (!pattern) return fail("sink_tiff_g4: null pattern"), nullptr;
+  if (dpi < 0 || dpi > 1200) return fail("sink_tiff_g4: dpi %d outside 0..1200", dpi), nullptr;
+  std::string fmt;
+  if (!output_pattern(pattern, &fmt)) return nullptr;
+  UphipSink* k = new UphipSink();
+  k->pattern = fmt;
+  k->wrap = wrap;
+  k->g4 = true;
+  k->pdf_dpi = dpi ? dpi : 300;
+  return k;
+}
+
+UphipSink* uphip_sink_pdf_bilevel(const char* path, const UphipPdfMetadata* meta, int32_t dpi) {
+  if (!path) return fail("sink_pdf_bilevel: null path"), nullptr;
+  if (dpi < 0 || dpi > 1200) return fail("sink_pdf_bilevel: dpi %d outside 0..1200", dpi), nullptr;
+  uph::pdf::Meta m;
+  if (meta) {
+    const char* f[8] = {meta->title,   meta->author,   meta->subject,       meta->keywords,
+                        meta->creator, meta->producer, meta->creation_date, meta->modification_date};
+    std::string* o[8] = {&m.title,   &m.author,   &m.subject,       &m.keywords,
+                         &m.creator, &m.producer, &m.creation_date, &m.modification_date};
+    for (int i = 0; i < 8; i++)
+      if (f[i]) {
+        *o[i] = f[i];
+        m.has[i] = true;
+      }
+  }
+  std::unique_ptr<uph::pdf::Writer> w(new uph::pdf::Writer());
+  if (!w->create(path, meta ? &m : nullptr, dpi ? dpi : 300)) return nullptr;
+  UphipSink* k = new UphipSink();
+  k->pdfw = std::move(w);
+  k->pdf_dpi = dpi ? dpi : 300;
+  k->g4 = true;
+  return k;
+}
+
+int uphip_tiff_g4_write(const char* path, const uint8_t* data, size_t len, int32_t width, int32_t height,
+                        int32_t dpi) {
+  if (!path || !data || !len) return fail("tiff_g4_write: null argument"), -1;
+  if (width <= 0 || height <= 0) return fail("tiff_g4_write: invalid size %dx%d", width, height), -1;
+  if (dpi < 0 || dpi > 1200) return fail("tiff_g4_write: dpi %d outside 0..1200", dpi), -1;
+  return write_tiff_g4(path, data, len, width, height, dpi ? dpi : 300) ? 0 : -1;
+}
+
 int uphip_sink_finish(UphipSink* k) {
   if (!k) return fail("sink_finish: null sink"), -1;
   if (!k->pdfw) return 0;
@@ -535,7 +635,7 @@ struct Slot {
   int64_t last_first = -1;  // the chunk whose outputs the batch holds (uphip_runner_slot_chunk)
   int32_t last_count = 0;
   std::vector<char> failed;  // per sheet of the chunk
-  // JPEG sink: the chunk's packed files (pinned) and each page's size / offset
+  // JPEG and Group 4 sinks: the chunk's packed files (pinned) and each page's size / offset
   uint8_t* hjpg = nullptr;
   size_t hjpg_cap = 0;
   std::vector<int64_t> jsize, joff;
@@ -674,7 +774,10 @@ bool write_file(const std::string& path, const uint8_t* p, size_t n) {
 // page of the sink's PDF (the page accumulator's writes,
 // pdf_page_accumulator.c:44-62; here straight from the store task, the
 // writer orders the page tree).
-bool sink_write(const UphipSink* k, int64_t idx, const uint8_t* p, size_t n) {
+bool sink_write(const UphipSink* k, int64_t idx, const uint8_t* p, size_t n, int32_t w = 0, int32_t h = 0) {
+  if (k->g4)  // a Group 4 stream has no header: the caller gives the page's size
+    return k->pdfw ? k->pdfw->add_page(idx, uph::pdf::kCcitt, p, n, w, h, 0, 0, k->pdf_dpi)
+                   : write_tiff_g4(sink_path(k, idx), p, n, w, h, k->pdf_dpi);
   if (!k->pdfw) return write_file(sink_path(k, idx), p, n);
   UphipPnmInfo g{0, 0, 0};
   if (k->jpeg ? !uph::jpeg_probe_mem(p, n, "output page", &g) : !uph::j2k::probe(p, n, "output page", &g))
@@ -709,6 +812,35 @@ void store_jpeg_sheet(UphipRunner* r, const UphipSink* k, int device, UphipBatch
     if (n <= 0 ||
         uphip_jpeg_encode(src, pitch, w, h, fmt, k->quality, k->sampling, file.data(), n) != n ||
         !sink_write(k, job * oc + j, file.data(), file.size()))
+      *ok = false;
+  }
+}
+
+// The Group 4 pages of sheet s of a slot's chunk, as store_jpeg_sheet: from
+// the chunk's packed download, or -- a page larger than its share of the
+// batch's encode buffer -- coded again on its own from the batch's sheet.
+void store_g4_sheet(UphipRunner* r, const UphipSink* k, int device, UphipBatch* b, int64_t job, int s,
+                    const uint8_t* packed, const std::vector<int64_t>& size,
+                    const std::vector<int64_t>& off, bool* ok) {
+  const int oc = r->opts.output_count < 1 ? 1 : r->opts.output_count;
+  const int32_t pw = r->out_w / oc;
+  for (int j = 0; j < oc; j++) {
+    const int i = s * oc + j;
+    if (size[(size_t)i] > 0) {
+      if (!sink_write(k, job * oc + j, packed + off[(size_t)i], (size_t)size[(size_t)i], pw, r->out_h))
+        *ok = false;
+      continue;
+    }
+    int64_t pitch = 0;
+    const void* src = uphip_set_device(device) == 0 ? uphip_batch_output_ptr(b, s, &pitch) : nullptr;
+    if (!src) {
+      *ok = false;
+      continue;
+    }
+    const int64_t n = uphip_g4_encode(src, pitch, j * pw, pw, r->out_h, nullptr, 0);
+    std::vector<uint8_t> file(n > 0 ? (size_t)n : 0);
+    if (n <= 0 || uphip_g4_encode(src, pitch, j * pw, pw, r->out_h, file.data(), n) != n ||
+        !sink_write(k, job * oc + j, file.data(), file.size(), pw, r->out_h))
       *ok = false;
   }
 }
@@ -1461,6 +1593,9 @@ int uphip_runner_run_device(UphipRunner* r, const UphipDevicePages* shards, int3
 
 int uphip_runner_run_host(UphipRunner* r, int64_t njobs, UphipSource* src, UphipSink* sink) {
   if (!r || !src || !sink || njobs < 0) return fail("runner_run_host: bad arguments"), -1;
+  if (sink->g4 && r->out_fmt != UPHIP_FMT_MONOWHITE)
+    return fail("runner_run_host: a Group 4 sink takes bilevel sheets and this runner's leave in format %d: "
+                "set output_pixel_format to UPHIP_FMT_MONOWHITE", r->out_fmt), -1;
   const int S = r->geo.capacity;
   const int nin = r->opts.input_count;
   if (!r->staged) {  // pinned staging per slot, laid out like the batch's input slots
@@ -1608,7 +1743,8 @@ int uphip_runner_run_host(UphipRunner* r, int64_t njobs, UphipSource* src, Uphip
                   uphip_batch_run_device(sl->b, sl->count, sl->din, src->linesize,
                                          src->page_stride) != 0 ||
                   (sink->jpeg &&
-                   uphip_batch_encode_jpeg_async(sl->b, sink->quality, sink->sampling) != 0)) {
+                   uphip_batch_encode_jpeg_async(sl->b, sink->quality, sink->sampling) != 0) ||
+                  (sink->g4 && uphip_batch_encode_g4_async(sl->b) != 0)) {
                 note("run failed");
                 for (int s = 0; s < sl->count; s++) sl->failed[(size_t)s] |= 1;
                 phase[k] = STORING;
@@ -1650,7 +1786,8 @@ int uphip_runner_run_host(UphipRunner* r, int64_t njobs, UphipSource* src, Uphip
             if (!upload_staging(r, sl, sl->count * nin) || !jpeg_submit(sl, sl->count * nin) ||
                 uphip_batch_run(sl->b, sl->count) != 0 ||
                 (sink->jpeg &&
-                 uphip_batch_encode_jpeg_async(sl->b, sink->quality, sink->sampling) != 0)) {
+                 uphip_batch_encode_jpeg_async(sl->b, sink->quality, sink->sampling) != 0) ||
+                (sink->g4 && uphip_batch_encode_g4_async(sl->b) != 0)) {
               note("run failed");
               for (int s = 0; s < sl->count; s++) sl->failed[(size_t)s] |= 1;
               phase[k] = STORING;  // accounted (all failed) on the next pass
@@ -1690,13 +1827,14 @@ int uphip_runner_run_host(UphipRunner* r, int64_t njobs, UphipSource* src, Uphip
             sl->direct_out = dsnk && clean;
             uint8_t* dst = sl->direct_out ? sink->base + sl->first * sink->sheet_stride : sl->hout;
             bool queued;
-            if (sink->jpeg) {
+            if (sink->jpeg || sink->g4) {
               // only the encoded files come back: sizes (already on the
               // host), then one copy of the packed files
               const int npg = sl->count * oc;
               sl->jsize.assign((size_t)npg, -1);
               sl->joff.assign((size_t)npg, 0);
-              const int64_t total = uphip_batch_jpeg_sizes(sl->b, sl->jsize.data(), npg);
+              const int64_t total = sink->g4 ? uphip_batch_g4_sizes(sl->b, sl->jsize.data(), npg)
+                                             : uphip_batch_jpeg_sizes(sl->b, sl->jsize.data(), npg);
               int64_t o = 0;
               for (int i = 0; i < npg; i++) {
                 sl->joff[(size_t)i] = o;
@@ -1711,7 +1849,8 @@ int uphip_runner_run_host(UphipRunner* r, int64_t njobs, UphipSource* src, Uphip
                 queued = UPH_HIP(hipHostMalloc((void**)&sl->hjpg, cap, hipHostMallocDefault));
                 if (queued) sl->hjpg_cap = cap;
               }
-              queued = queued && uphip_batch_jpeg_download_async(sl->b, sl->hjpg, (int64_t)sl->hjpg_cap) == 0;
+              queued = queued && (sink->g4 ? uphip_batch_g4_download_async(sl->b, sl->hjpg, (int64_t)sl->hjpg_cap)
+                                           : uphip_batch_jpeg_download_async(sl->b, sl->hjpg, (int64_t)sl->hjpg_cap)) == 0;
             } else if (sink->jp2) {
               // the chunk's pages coded on the device; the store tasks write
               queued = jp2_chunk_submit(r, sl, sl->count * oc);
@@ -1753,6 +1892,9 @@ int uphip_runner_run_host(UphipRunner* r, int64_t njobs, UphipSource* src, Uphip
                 if (sink->jpeg)
                   store_jpeg_sheet(r, sink, dc.device, sl->b, sl->first + s, s, sl->hjpg, sl->jsize,
                                    sl->joff, &good);
+                else if (sink->g4)
+                  store_g4_sheet(r, sink, dc.device, sl->b, sl->first + s, s, sl->hjpg, sl->jsize, sl->joff,
+                                 &good);
                 else if (sink->jp2)
                   store_jp2_chunk_sheet(r, sink, dc.device, sl, sl->first + s, s, &good);
                 else

@@ -66,6 +66,9 @@ EXPORTED = [
     "uphip_pdf_writer_page_count", "uphip_pdf_writer_close", "uphip_pdf_writer_abort",
     "uphip_source_pdf", "uphip_source_page_count", "uphip_sink_pdf", "uphip_sink_finish",
     "uphip_jbig2_decode", "uphip_jbig2_free_image",
+    "uphip_g4_encode_host", "uphip_g4_encode", "uphip_batch_encode_g4_async", "uphip_batch_g4_sizes",
+    "uphip_batch_g4_download_async", "uphip_pdf_writer_add_page_g4", "uphip_sink_tiff_g4",
+    "uphip_sink_pdf_bilevel", "uphip_tiff_g4_write",
 ]
 
 
@@ -262,6 +265,19 @@ def load_library(path=LIB_PATH):
         "uphip_sink_pdf": (C.c_void_p, [C.c_char_p, C.POINTER(A.PdfMetadata), C.c_int32, C.c_int32,
                                         C.c_int32]),
         "uphip_sink_finish": (C.c_int, [C.c_void_p]),
+        "uphip_g4_encode_host": (C.c_int64, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                             C.c_void_p, C.c_int64]),
+        "uphip_g4_encode": (C.c_int64, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                        C.c_void_p, C.c_int64]),
+        "uphip_batch_encode_g4_async": (C.c_int, [C.c_void_p]),
+        "uphip_batch_g4_sizes": (C.c_int64, [C.c_void_p, C.POINTER(C.c_int64), C.c_int32]),
+        "uphip_batch_g4_download_async": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
+        "uphip_pdf_writer_add_page_g4": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t,
+                                                   C.c_int32, C.c_int32, C.c_int32]),
+        "uphip_sink_tiff_g4": (C.c_void_p, [C.c_char_p, C.c_int64, C.c_int32]),
+        "uphip_tiff_g4_write": (C.c_int, [C.c_char_p, C.c_void_p, C.c_size_t, C.c_int32, C.c_int32,
+                                          C.c_int32]),
+        "uphip_sink_pdf_bilevel": (C.c_void_p, [C.c_char_p, C.POINTER(A.PdfMetadata), C.c_int32]),
     }
     for name, (res, args) in sig.items():
         if not hasattr(L, name):

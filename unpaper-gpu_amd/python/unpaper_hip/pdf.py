@@ -190,6 +190,11 @@ class PdfWriter:
         self._call(load_library().uphip_pdf_writer_add_page_jp2(self.handle, data, len(data), width,
                                                                 height, dpi), "add_page_jp2 failed")
 
+    def add_page_g4(self, data: bytes, width, height, dpi=0):
+        """A bilevel page from its CCITT Group 4 stream (1 = black)."""
+        self._call(load_library().uphip_pdf_writer_add_page_g4(self.handle, data, len(data), width,
+                                                               height, dpi), "add_page_g4 failed")
+
     def add_page_pixels(self, pixels, width, height, stride, fmt, dpi=0):
         """pixels: a contiguous uint8 numpy array, rows `stride` bytes apart;
         fmt PIXEL_GRAY8 or PIXEL_RGB24."""

@@ -141,6 +141,44 @@ class Batch:
             _check(self.lib)
         return src.value, pitch.value, w.value, h.value, f.value
 
+    def encode_g4(self):
+        """Queue the bilevel output branch on the last run's pages: CCITT
+        Group 4 streams (uphip_batch_encode_g4_async; MONOWHITE output only)."""
+        if self.lib.uphip_batch_encode_g4_async(self.handle) != 0:
+            _check(self.lib)
+            raise UnpaperHipError("batch_encode_g4 failed")
+
+    def g4_files(self, pages):
+        """The streams of the last encode_g4 (None for a page larger than its
+        share of the encode buffer: g4_encode from output_ptr)."""
+        L = self.lib
+        self.wait()
+        sizes = (C.c_int64 * pages)()
+        total = L.uphip_batch_g4_sizes(self.handle, sizes, pages)
+        _check(L)
+        buf = np.zeros(max(total, 1), np.uint8)
+        if total > 0 and L.uphip_batch_g4_download_async(self.handle, buf.ctypes.data, total) != 0:
+            _check(L)
+        self.wait()
+        out, off = [], 0
+        for i in range(pages):
+            n = sizes[i]
+            if n > 0:
+                out.append(buf[off:off + n].tobytes())
+                off += n
+            else:
+                out.append(None)
+        return out
+
+    def output_ptr(self, sheet):
+        """(device pointer, pitch) of output sheet `sheet` (waits for the run)."""
+        pitch = C.c_int64()
+        p = self.lib.uphip_batch_output_ptr(self.handle, sheet, C.byref(pitch))
+        if not p:
+            _check(self.lib)
+            raise UnpaperHipError("batch_output_ptr failed")
+        return p, pitch.value
+
     def report(self, sheet):
         r = A.SheetReport()
         self.lib.uphip_batch_get_report(self.handle, sheet, C.byref(r))
@@ -427,6 +465,66 @@ def sink_pdf(path, meta=None, dpi=0, quality=0, mode=0):
     if not h:
         raise UnpaperHipError("sink_pdf failed")
     return _PdfSink(h, L.uphip_sink_destroy, (m, keep))
+
+
+def sink_tiff_g4(pattern, wrap=0, dpi=0):
+    """One CCITT Group 4 TIFF per output page, coded on the device
+    (uphip_sink_tiff_g4; bilevel output only; dpi 0 = 300)."""
+    L = load_library()
+    h = L.uphip_sink_tiff_g4(pattern.encode(), wrap, dpi)
+    _check(L)
+    if not h:
+        raise UnpaperHipError("sink_tiff_g4 failed")
+    return _Handle(h, L.uphip_sink_destroy)
+
+
+def sink_pdf_bilevel(path, meta=None, dpi=0):
+    """All output pages into one PDF of CCITT Group 4 images
+    (uphip_sink_pdf_bilevel; bilevel output only; dpi 0 = 300).  Call
+    finish() after the run."""
+    from .pdf import _meta_struct
+    L = load_library()
+    m, keep = _meta_struct(meta)
+    h = L.uphip_sink_pdf_bilevel(path.encode(), C.byref(m) if m is not None else None, dpi)
+    _check(L)
+    if not h:
+        raise UnpaperHipError("sink_pdf_bilevel failed")
+    return _PdfSink(h, L.uphip_sink_destroy, (m, keep))
+
+
+def _g4(fn, ptr, pitch, bit_offset, width, height):
+    L = load_library()
+    n = fn(ptr, pitch, bit_offset, width, height, None, 0)
+    _check(L)
+    if n <= 0:
+        raise UnpaperHipError("g4 encode failed")
+    buf = np.zeros(n, np.uint8)
+    m = fn(ptr, pitch, bit_offset, width, height, buf.ctypes.data, n)
+    _check(L)
+    if m != n:
+        raise UnpaperHipError("g4 encode: size changed between calls")
+    return buf.tobytes()
+
+
+def g4_encode(device_ptr, pitch, width, height, bit_offset=0):
+    """uphip_g4_encode: packed 1-bit rows in device memory (1 = black, pixel
+    0 at bit `bit_offset` of a row) -> CCITT Group 4 stream."""
+    return _g4(load_library().uphip_g4_encode, device_ptr, pitch, bit_offset, width, height)
+
+
+def g4_encode_host(rows, width, bit_offset=0):
+    """uphip_g4_encode_host: a 2-D uint8 array of packed rows (no device)."""
+    rows = np.ascontiguousarray(rows, np.uint8)
+    return _g4(load_library().uphip_g4_encode_host, rows.ctypes.data, rows.shape[1], bit_offset, width,
+               rows.shape[0])
+
+
+def tiff_g4_write(path, stream: bytes, width, height, dpi=0):
+    """uphip_tiff_g4_write: a Group 4 stream as a one-strip TIFF file."""
+    L = load_library()
+    if L.uphip_tiff_g4_write(path.encode(), stream, len(stream), width, height, dpi) != 0:
+        _check(L)
+        raise UnpaperHipError("tiff_g4_write failed")
 
 
 def sink_discard():
