@@ -7,6 +7,8 @@
 #                      restatement against the host libm (test)
 #   make sanitize   -> tests/c/_build/sanitize: the oracle + the host codec
 #                      under ASan/UBSan (host code only, no GPU)
+#   make sanitize_png -> tests/c/_build/png_enc_main: the lossless PNG encoder's
+#                      host twin under ASan/UBSan, stand-alone (host code only)
 #   make lib DIAG=1 -> the same library with the timing diagnostics of
 #                      csrc/common.h (UPHIP_DIAG_*) compiled in; tuning only,
 #                      built into its own object dir.  The default build has none.
@@ -62,7 +64,7 @@ LLVMCC     := /opt/rocm/lib/llvm/bin/clang
 SANFLAGS   := -fsanitize=address,undefined -fno-sanitize-recover=undefined \
               -fno-omit-frame-pointer -g -O1
 
-.PHONY: all lib oracle ctest sanitize libm_check jdec_emul j2k_emul clean
+.PHONY: all lib oracle ctest sanitize sanitize_png libm_check jdec_emul j2k_emul clean
 all: lib oracle ctest libm_check jdec_emul j2k_emul
 
 lib: $(LIB)
@@ -150,6 +152,17 @@ $(J2K_EMUL): tests/c/j2k_emul.cpp $(CSRC)/j2k_dwt.h $(CSRC)/j2k.h $(CSRC)/j2k_t1
 
 sanitize: $(SANITIZE)
 	ASAN_OPTIONS=detect_leaks=1 UBSAN_OPTIONS=print_stacktrace=1 $(SANITIZE) $(CURDIR)/tests/c/_build/san $(CURDIR)/tests/golden/reference
+
+# the PNG encoder's host twin with its own main and error reporting: no
+# device code, no other part of the library
+PNG_ENC_MAIN := tests/c/_build/png_enc_main
+$(PNG_ENC_MAIN): tests/c/png_enc_main.cpp $(CSRC)/png_enc.cpp $(CSRC)/png_enc_core.h $(CSRC)/png_enc.h $(HDRS)
+	@mkdir -p tests/c/_build
+	$(HIPCC) --cuda-host-only -x hip $(SANFLAGS) -std=c++17 -Wall -Wno-unused-function -Wno-unused-result \
+	  -Wno-unused-value -Iinclude -I$(CSRC) tests/c/png_enc_main.cpp $(CSRC)/png_enc.cpp -o $@ -lz
+
+sanitize_png: $(PNG_ENC_MAIN)
+	ASAN_OPTIONS=detect_leaks=1 UBSAN_OPTIONS=print_stacktrace=1 $(PNG_ENC_MAIN)
 
 clean:
 	rm -rf $(PKG)/build $(PKG)/build_diag $(PKG)/lib $(PKG)/lib_diag oracle/_build oracle/_ref tests/c/_build

@@ -483,10 +483,30 @@ int uphip_batch_jpeg_page(UphipBatch *batch, int32_t page, const void **device_s
 int uphip_batch_encode_g4_async(UphipBatch *batch);
 int64_t uphip_batch_g4_sizes(UphipBatch *batch, int64_t *sizes, int32_t max_pages);
 int uphip_batch_g4_download_async(UphipBatch *batch, void *host, int64_t capacity);
+/* The lossless output branch for a whole batch, the peer of the Group 4 three
+ * for any output format (no reference peer: the reference's saveImage writes
+ * PNM only): queued on the batch stream after uphip_batch_run*, it codes
+ * every output page of the last run (page j of a sheet starts at pixel
+ * j * width / output_count of the sheet's rows) as the zlib stream of a PNG
+ * IDAT chunk (uphip_png_encode) and packs the streams one after another in
+ * device memory, then copies their sizes to the host.  After the stream is
+ * idle:
+ *   png_sizes:           sizes[i] of page i (always > 0: a page that would
+ *                        not shrink goes out as stored blocks, so no page
+ *                        fails for size); returns the packed total
+ *   png_download_async:  the packed streams into host memory (total bytes);
+ *                        uphip_png_wrap or uphip_pdf_writer_add_page_flate
+ *                        makes a file or a PDF page of each.
+ * The encode buffers are allocated by the first encode and counted by
+ * uphip_batch_device_bytes from then on. */
+int uphip_batch_encode_png_async(UphipBatch *batch);
+int64_t uphip_batch_png_sizes(UphipBatch *batch, int64_t *sizes, int32_t max_pages);
+int uphip_batch_png_download_async(UphipBatch *batch, void *host, int64_t capacity);
 /* Row pitch of the output sheets on the device: host staging with this
  * linesize (and pitch * height per sheet) downloads as linear DMA copies. */
 int uphip_batch_output_pitch(UphipBatch *batch, int64_t *pitch);
-/* Device memory the batch holds (planes, inputs, scratch, tables). */
+/* Device memory the batch holds (planes, inputs, scratch, tables, and the
+ * buffers of the lossless encoder once uphip_batch_encode_png_async ran). */
 int uphip_batch_device_bytes(UphipBatch *batch, int64_t *bytes);
 
 /* ---------------------------------------------------------------------------
@@ -509,7 +529,8 @@ int uphip_pnm_write(const char *path, const void *src, int64_t linesize,
  * MONOBLACK, 2/4/8-bit gray -> GRAY8, gray+alpha (or 8-bit gray + tRNS) ->
  * Y400A, RGB -> RGB24, palette -> RGB24 (the PAL8 case, file.c:110-120);
  * 16-bit samples and RGBA fail like loadImage's "unsupported pixel format".
- * Adam7 interlacing supported.  Output stays PNM (saveImage, file.c:260-300). */
+ * Adam7 interlacing supported.  saveImage writes PNM only (file.c:260-300);
+ * PNG output is uphip_png_encode* below. */
 int uphip_png_probe(const char *path, UphipPnmInfo *info);
 int uphip_png_read(const char *path, void *dst, int64_t linesize,
                    const UphipPnmInfo *expect);
@@ -611,6 +632,32 @@ int64_t uphip_g4_encode(const void *device_src, int64_t pitch, int32_t bit_offse
  * classic, little-endian, one strip; dpi 0 = 300.  0 / -1. */
 int uphip_tiff_g4_write(const char *path, const uint8_t *data, size_t len, int32_t width,
                         int32_t height, int32_t dpi);
+/* Lossless PNG encode (no reference peer: the reference's saveImage writes
+ * PNM only).  GRAY8 -> colour type 0, RGB24 -> 2, Y400A -> 4, depth 8;
+ * MONOBLACK and MONOWHITE -> type 0, depth 1 (MONOWHITE bits inverted: in PNG
+ * 1 is white; pad bits 0).  `offset`: pixel 0 of a row is bit `offset` of it
+ * for the bilevel formats and bits outside [offset, offset + width) are not
+ * read as pixels; it must be 0 for the byte formats (offset the pointer).
+ * Per row the filter None, Sub or Up with the least sum of absolute values;
+ * one dynamic-Huffman Deflate block per image over a deterministic LZ77 parse
+ * (csrc/png_enc_core.h), or stored blocks when that would not be smaller.
+ * The result is a whole file: signature, IHDR, pHYs (when dpi > 0:
+ * round(dpi / 0.0254) pixels per metre), one IDAT, IEND.  Returns the file's
+ * size; out = NULL sizes a buffer; -1 on error (also when `capacity` is too
+ * small).
+ *   uphip_png_encode_host: rows `stride` apart in host memory; needs no device.
+ *   uphip_png_encode:      rows `pitch` apart in device memory, coded on the
+ *                          current device to the same bytes; synchronous. */
+int64_t uphip_png_encode_host(const void *pixels, int64_t stride, int32_t offset, int32_t width,
+                              int32_t height, int32_t format, int32_t dpi, void *out,
+                              int64_t capacity);
+int64_t uphip_png_encode(const void *device_src, int64_t pitch, int32_t offset, int32_t width,
+                         int32_t height, int32_t format, int32_t dpi, void *out, int64_t capacity);
+/* A zlib stream of the encoder (uphip_batch_png_download_async) as the PNG
+ * file of a width x height image of `format`; on the host, chunk CRCs
+ * included.  Sizes and errors as uphip_png_encode.  No reference peer. */
+int64_t uphip_png_wrap(const void *stream, int64_t len, int32_t width, int32_t height,
+                       int32_t format, int32_t dpi, void *out, int64_t capacity);
 /* Any codec, picked by the file's signature (PNG, JPEG, JPEG 2000 or PNM). */
 int uphip_image_probe(const char *path, UphipPnmInfo *info);
 int uphip_image_read(const char *path, void *dst, int64_t linesize,
@@ -708,6 +755,14 @@ int uphip_pdf_writer_add_page_pixels(UphipPdfWriter *writer, const uint8_t *pixe
  * the image also carries /Decode [1 0]: 1 paints black. */
 int uphip_pdf_writer_add_page_g4(UphipPdfWriter *writer, const uint8_t *data, size_t len,
                                  int32_t width, int32_t height, int32_t dpi);
+/* A lossless page from the encoder's zlib stream (uphip_png_encode's IDAT
+ * payload, uphip_batch_png_download_async): an image with /Filter
+ * /FlateDecode /DecodeParms << /Predictor 15 /Colors n /BitsPerComponent b
+ * /Columns width >>, /DeviceGray (GRAY8, MONOBLACK, MONOWHITE: the stream's
+ * bits are in PNG sense, 1 = white) or /DeviceRGB (RGB24).  Y400A fails: PDF
+ * images carry no alpha sample.  No reference peer. */
+int uphip_pdf_writer_add_page_flate(UphipPdfWriter *writer, const uint8_t *data, size_t len,
+                                    int32_t width, int32_t height, int32_t format, int32_t dpi);
 int uphip_pdf_writer_page_count(UphipPdfWriter *writer);
 /* lib/jbig2_decode.h:19-45 (jbig2_decode over jbig2dec): an embedded JBIG2
  * stream (+ its globals) to a 1-bit page, MSB first, 1 = black, rows
@@ -833,6 +888,21 @@ UphipSink *uphip_sink_pdf(const char *path, const UphipPdfMetadata *meta, int32_
  *                           pages, dpi, finish and destroy as uphip_sink_pdf. */
 UphipSink *uphip_sink_tiff_g4(const char *pattern, int64_t wrap, int32_t dpi);
 UphipSink *uphip_sink_pdf_bilevel(const char *path, const UphipPdfMetadata *meta, int32_t dpi);
+/* Lossless output in any output format (no reference peer: the reference's
+ * saveImage writes PNM only).  The pages are coded on the device right after
+ * their batch (uphip_batch_encode_png_async) and only the streams cross PCIe;
+ * the store tasks wrap and write them.
+ *   uphip_sink_png:          one PNG file per output page (uphip_png_wrap),
+ *                            pHYs from `dpi` (0 = none); names as
+ *                            uphip_sink_pnm.
+ *   uphip_sink_pdf_lossless: one PDF of /FlateDecode pages
+ *                            (uphip_pdf_writer_add_page_flate); ordering,
+ *                            skipped pages, dpi (0 = 300), finish and destroy
+ *                            as uphip_sink_pdf.  uphip_runner_run_host refuses
+ *                            Y400A sheets before it starts, naming
+ *                            output_pixel_format. */
+UphipSink *uphip_sink_png(const char *pattern, int64_t wrap, int32_t dpi);
+UphipSink *uphip_sink_pdf_lossless(const char *path, const UphipPdfMetadata *meta, int32_t dpi);
 int uphip_sink_finish(UphipSink *sink);
 void uphip_sink_destroy(UphipSink *sink);
 

@@ -1620,6 +1620,18 @@ bool Writer::create(const char* path, const Meta* meta, int dpi) {
   return put(head, sizeof(head) - 1);
 }
 
+bool flate_layout(int32_t format, int* components, int* bits) {
+  switch (format) {
+    case UPHIP_FMT_GRAY8: *components = 1; *bits = 8; return true;
+    case UPHIP_FMT_RGB24: *components = 3; *bits = 8; return true;
+    case UPHIP_FMT_MONOBLACK:
+    case UPHIP_FMT_MONOWHITE: *components = 1; *bits = 1; return true;
+    case UPHIP_FMT_Y400A:
+      return fail("pdf_writer: a Y400A page cannot be a Flate image: PDF images carry no alpha sample");
+    default: return fail("pdf_writer: unknown pixel format %d", format);
+  }
+}
+
 bool Writer::add_page(int64_t index, int kind, const uint8_t* data, size_t len, int width, int height,
                       int stride, int components, int dpi) {
   if (!data || !len) return fail("pdf_writer: Invalid arguments");
@@ -1651,6 +1663,13 @@ bool Writer::add_page(int64_t index, int kind, const uint8_t* data, size_t len, 
     bpc = 1;
     snprintf(parms, sizeof(parms), " /DecodeParms << /K -1 /Columns %d /Rows %d /BlackIs1 true >> /Decode [1 0]",
              width, height);
+  } else if (kind == kPng) {
+    // a zlib stream of PNG-filtered rows (png_enc_core.h), as it is
+    if (components != 1 && components != 3) return fail("pdf_writer: a Flate page has 1 or 3 components");
+    bpc = stride == 1 ? 1 : 8;
+    filter = "FlateDecode";
+    snprintf(parms, sizeof(parms), " /DecodeParms << /Predictor 15 /Colors %d /BitsPerComponent %d /Columns %d >>",
+             components, bpc, width);
   } else if (kind == kRaw) {
     if (components != 1 && components != 3) return fail("pdf_writer: pixels must have 1 or 3 components");
     const size_t rb = (size_t)width * components;
@@ -2049,6 +2068,14 @@ int uphip_pdf_writer_add_page_g4(UphipPdfWriter* w, const uint8_t* data, size_t 
                                  int32_t height, int32_t dpi) {
   if (!w) return fail("pdf_writer: Invalid arguments"), -1;
   return w->w.add_page_next(uph::pdf::kCcitt, data, len, width, height, 0, 0, dpi) ? 0 : -1;
+}
+
+int uphip_pdf_writer_add_page_flate(UphipPdfWriter* w, const uint8_t* data, size_t len, int32_t width,
+                                    int32_t height, int32_t format, int32_t dpi) {
+  if (!w) return fail("pdf_writer: Invalid arguments"), -1;
+  int comps = 0, bits = 0;
+  if (!uph::pdf::flate_layout(format, &comps, &bits)) return -1;
+  return w->w.add_page_next(uph::pdf::kPng, data, len, width, height, bits, comps, dpi) ? 0 : -1;
 }
 
 int uphip_pdf_writer_add_page_pixels(UphipPdfWriter* w, const uint8_t* pixels, int32_t width, int32_t height,

@@ -172,12 +172,18 @@ bool page_geometry(Document& doc, int page, int32_t dpi, PageImage* im, UphipPnm
 // waits for those writes, writes the page tree in page-index order, the
 // cross-reference table and trailer, and renames the file into place;
 // abort() (or destruction without close) removes it.  Thread-safe.
+// Components and bits per component of a Flate page of `format`
+// (flate_layout fails for Y400A and unknown formats).
+bool flate_layout(int32_t format, int* components, int* bits);
+
 class Writer {
  public:
   ~Writer();
   bool create(const char* path, const Meta* meta, int dpi);
-  // kind: kJpeg, kJp2, kCcitt (a Group 4 stream, 1 = black: ccitt::encode) or
-  // kRaw (pixels: components 1 or 3, `stride` apart)
+  // kind: kJpeg, kJp2, kCcitt (a Group 4 stream, 1 = black: ccitt::encode),
+  // kPng (a zlib stream of PNG-filtered rows: components 1 or 3, `stride`
+  // the bits per component, 1 or 8) or kRaw (pixels: components 1 or 3,
+  // `stride` apart)
   bool add_page(int64_t index, int kind, const uint8_t* data, size_t len, int width, int height,
                 int stride, int components, int dpi);
   bool add_page_next(int kind, const uint8_t* data, size_t len, int width, int height, int stride,

@@ -18,6 +18,7 @@
 
 #include "filters.h"
 #include "g4_enc.h"
+#include "png_enc.h"
 #include "jpeg_enc.h"
 #include "libm_glibc.h"
 #include "runtime.h"
@@ -476,6 +477,9 @@ struct UphipBatch {
   // bilevel output branch (uphip_batch_encode_g4_async)
   G4Context* g4 = nullptr;
   int g4_pages = 0;
+  // lossless output branch (uphip_batch_encode_png_async)
+  PngContext* png = nullptr;
+  int png_pages = 0;
 };
 
 namespace {
@@ -1582,6 +1586,7 @@ void uphip_batch_destroy(UphipBatch* b) {
   for (void* p : b->allocs) hipFree(p);
   delete b->jenc;
   delete b->g4;
+  delete b->png;
   if (b->st) hipStreamDestroy(b->st);
   delete b;
 }
@@ -1598,7 +1603,7 @@ int uphip_batch_output_info(UphipBatch* b, int32_t* width, int32_t* height, int3
 
 int uphip_batch_device_bytes(UphipBatch* b, int64_t* bytes) {
   if (!b || !bytes) return fail("batch_device_bytes: null argument"), -1;
-  *bytes = (int64_t)b->dev_bytes;
+  *bytes = (int64_t)(b->dev_bytes + (b->png ? b->png->device_bytes() : 0));
   return 0;
 }
 
@@ -1893,6 +1898,50 @@ int uphip_batch_g4_download_async(UphipBatch* b, void* host, int64_t capacity) {
   if (!host || capacity < total) return fail("batch_g4_download: buffer too small"), -1;
   hipSetDevice(b->device);
   return UPH_HIP(hipMemcpyAsync(host, b->g4->out, (size_t)total, hipMemcpyDeviceToHost, b->st)) ? 0 : -1;
+}
+
+// ---- lossless output branch: PNG / Flate (png_enc.h) ----------------------
+int uphip_batch_encode_png_async(UphipBatch* b) {
+  if (!b || b->last_count <= 0) return fail("batch_encode_png: nothing to encode"), -1;
+  hipSetDevice(b->device);
+  const int oc = b->o.output_count < 1 ? 1 : b->o.output_count;
+  const int32_t pw = b->out_w / oc;
+  if (pw <= 0) return fail("batch_encode_png: empty pages"), -1;
+  if (!b->png) b->png = new PngContext();
+  PngPages pg;
+  if (b->out) {
+    pg = PngPages{{b->out, nullptr}, nullptr, 0, b->out_stride, b->out_pitch, oc, b->out_w, 0,
+                  (int32_t)b->out_fmt, pw, b->out_h, b->last_count * oc};
+  } else {
+    // the sheets lie in the plane their ctl names (as uphip_batch_download_async)
+    pg = PngPages{{b->planes[0], b->planes[1]}, &b->ctl[0].cur, (int64_t)(sizeof(SheetCtl) / sizeof(int32_t)),
+                  b->plane_stride, b->pitch, oc, b->out_w, 0, (int32_t)b->out_fmt, pw, b->out_h,
+                  b->last_count * oc};
+  }
+  if (!b->png->encode_async(pg, b->st)) return -1;
+  b->png_pages = pg.npages;
+  return 0;
+}
+
+int64_t uphip_batch_png_sizes(UphipBatch* b, int64_t* sizes, int32_t max_pages) {
+  if (!b || !b->png || b->png_pages <= 0) return fail("batch_png_sizes: no encode"), -1;
+  if (uphip_batch_query(b) != 1) return fail("batch_png_sizes: the encode has not finished"), -1;
+  int64_t total = 0;
+  for (int i = 0; i < b->png_pages; i++) {
+    const int64_t s = b->png->host_sizes[i];
+    if (s <= 0) return fail("batch_png_sizes: page %d has no size", i), -1;
+    if (sizes && i < max_pages) sizes[i] = s;
+    total += s;
+  }
+  return total;
+}
+
+int uphip_batch_png_download_async(UphipBatch* b, void* host, int64_t capacity) {
+  const int64_t total = uphip_batch_png_sizes(b, nullptr, 0);
+  if (total < 0) return -1;
+  if (!host || capacity < total) return fail("batch_png_download: buffer too small"), -1;
+  hipSetDevice(b->device);
+  return UPH_HIP(hipMemcpyAsync(host, b->png->out, (size_t)total, hipMemcpyDeviceToHost, b->st)) ? 0 : -1;
 }
 
 int uphip_batch_set_timing(UphipBatch* b, int32_t enable) {

@@ -248,6 +248,10 @@ struct UphipSink {
   // CCITT Group 4 streams coded on the device from bilevel sheets
   // (uphip_sink_tiff_g4: a TIFF per page, at pdf_dpi; uphip_sink_pdf_bilevel)
   bool g4 = false;
+  // lossless zlib streams coded on the device from sheets of any format
+  // (uphip_sink_png: a PNG per page, pHYs from png_dpi; uphip_sink_pdf_lossless)
+  bool png = false;
+  int32_t png_dpi = 0;
   // one PDF of all the output pages (uphip_sink_pdf, uphip_sink_pdf_bilevel):
   // the encoded pages go to the writer instead of files
   std::unique_ptr<uph::pdf::Writer> pdfw;
@@ -554,6 +558,29 @@ UphipSink* uphip_sink_pdf_bilevel(const char* path, const UphipPdfMetadata* meta
   return k;
 }
 
+UphipSink* uphip_sink_png(const char* pattern, int64_t wrap, int32_t dpi) {
+  if (!pattern) return fail("sink_png: null pattern"), nullptr;
+  if (dpi < 0 || dpi > 1200) return fail("sink_png: dpi %d outside 0..1200", dpi), nullptr;
+  std::string fmt;
+  if (!output_pattern(pattern, &fmt)) return nullptr;
+  UphipSink* k = new UphipSink();
+  k->pattern = fmt;
+  k->wrap = wrap;
+  k->png = true;
+  k->png_dpi = dpi;
+  return k;
+}
+
+UphipSink* uphip_sink_pdf_lossless(const char* path, const UphipPdfMetadata* meta, int32_t dpi) {
+  if (!path) return fail("sink_pdf_lossless: null path"), nullptr;
+  if (dpi < 0 || dpi > 1200) return fail("sink_pdf_lossless: dpi %d outside 0..1200", dpi), nullptr;
+  UphipSink* k = uphip_sink_pdf_bilevel(path, meta, dpi);  // the same writer; the pages differ
+  if (!k) return nullptr;
+  k->g4 = false;
+  k->png = true;
+  return k;
+}
+
 int uphip_tiff_g4_write(const char* path, const uint8_t* data, size_t len, int32_t width, int32_t height,
                         int32_t dpi) {
   if (!path || !data || !len) return fail("tiff_g4_write: null argument"), -1;
@@ -812,6 +839,34 @@ void store_jpeg_sheet(UphipRunner* r, const UphipSink* k, int device, UphipBatch
     if (n <= 0 ||
         uphip_jpeg_encode(src, pitch, w, h, fmt, k->quality, k->sampling, file.data(), n) != n ||
         !sink_write(k, job * oc + j, file.data(), file.size()))
+      *ok = false;
+  }
+}
+
+// The lossless pages of sheet s of a slot's chunk from the chunk's packed
+// download: each zlib stream into its PNG file or its page of the sink's PDF.
+void store_png_sheet(UphipRunner* r, const UphipSink* k, int64_t job, int s, const uint8_t* packed,
+                     const std::vector<int64_t>& size, const std::vector<int64_t>& off, bool* ok) {
+  const int oc = r->opts.output_count < 1 ? 1 : r->opts.output_count;
+  const int32_t pw = r->out_w / oc;
+  for (int j = 0; j < oc; j++) {
+    const size_t i = (size_t)(s * oc + j);
+    const uint8_t* z = packed + off[i];
+    if (size[i] <= 0) {
+      *ok = false;
+      continue;
+    }
+    if (k->pdfw) {
+      int comps = 0, bits = 0;
+      if (!uph::pdf::flate_layout(r->out_fmt, &comps, &bits) ||
+          !k->pdfw->add_page(job * oc + j, uph::pdf::kPng, z, (size_t)size[i], pw, r->out_h, bits, comps, k->pdf_dpi))
+        *ok = false;
+      continue;
+    }
+    const int64_t n = uphip_png_wrap(z, size[i], pw, r->out_h, r->out_fmt, k->png_dpi, nullptr, 0);
+    std::vector<uint8_t> file(n > 0 ? (size_t)n : 0);
+    if (n <= 0 || uphip_png_wrap(z, size[i], pw, r->out_h, r->out_fmt, k->png_dpi, file.data(), n) != n ||
+        !write_file(sink_path(k, job * oc + j), file.data(), file.size()))
       *ok = false;
   }
 }
@@ -1596,6 +1651,13 @@ int uphip_runner_run_host(UphipRunner* r, int64_t njobs, UphipSource* src, Uphip
   if (sink->g4 && r->out_fmt != UPHIP_FMT_MONOWHITE)
     return fail("runner_run_host: a Group 4 sink takes bilevel sheets and this runner's leave in format %d: "
                 "set output_pixel_format to UPHIP_FMT_MONOWHITE", r->out_fmt), -1;
+  // the batch saves Y400A sheets as GRAY8 (saveImage's mapping); a PDF asked
+  // for gray with alpha would silently lose the alpha, so it is refused
+  if (sink->png && sink->pdfw &&
+      (r->opts.output_pixel_format == UPHIP_FMT_NONE ? r->geo.page_format : r->opts.output_pixel_format) ==
+          UPHIP_FMT_Y400A)
+    return fail("runner_run_host: a lossless PDF sink cannot take Y400A sheets (PDF images carry no alpha "
+                "sample): set output_pixel_format to another format"), -1;
   const int S = r->geo.capacity;
   const int nin = r->opts.input_count;
   if (!r->staged) {  // pinned staging per slot, laid out like the batch's input slots
@@ -1744,7 +1806,8 @@ int uphip_runner_run_host(UphipRunner* r, int64_t njobs, UphipSource* src, Uphip
                                          src->page_stride) != 0 ||
                   (sink->jpeg &&
                    uphip_batch_encode_jpeg_async(sl->b, sink->quality, sink->sampling) != 0) ||
-                  (sink->g4 && uphip_batch_encode_g4_async(sl->b) != 0)) {
+                  (sink->g4 && uphip_batch_encode_g4_async(sl->b) != 0) ||
+                  (sink->png && uphip_batch_encode_png_async(sl->b) != 0)) {
                 note("run failed");
                 for (int s = 0; s < sl->count; s++) sl->failed[(size_t)s] |= 1;
                 phase[k] = STORING;
@@ -1787,7 +1850,8 @@ int uphip_runner_run_host(UphipRunner* r, int64_t njobs, UphipSource* src, Uphip
                 uphip_batch_run(sl->b, sl->count) != 0 ||
                 (sink->jpeg &&
                  uphip_batch_encode_jpeg_async(sl->b, sink->quality, sink->sampling) != 0) ||
-                (sink->g4 && uphip_batch_encode_g4_async(sl->b) != 0)) {
+                (sink->g4 && uphip_batch_encode_g4_async(sl->b) != 0) ||
+                (sink->png && uphip_batch_encode_png_async(sl->b) != 0)) {
               note("run failed");
               for (int s = 0; s < sl->count; s++) sl->failed[(size_t)s] |= 1;
               phase[k] = STORING;  // accounted (all failed) on the next pass
@@ -1827,14 +1891,15 @@ int uphip_runner_run_host(UphipRunner* r, int64_t njobs, UphipSource* src, Uphip
             sl->direct_out = dsnk && clean;
             uint8_t* dst = sl->direct_out ? sink->base + sl->first * sink->sheet_stride : sl->hout;
             bool queued;
-            if (sink->jpeg || sink->g4) {
+            if (sink->jpeg || sink->g4 || sink->png) {
               // only the encoded files come back: sizes (already on the
               // host), then one copy of the packed files
               const int npg = sl->count * oc;
               sl->jsize.assign((size_t)npg, -1);
               sl->joff.assign((size_t)npg, 0);
-              const int64_t total = sink->g4 ? uphip_batch_g4_sizes(sl->b, sl->jsize.data(), npg)
-                                             : uphip_batch_jpeg_sizes(sl->b, sl->jsize.data(), npg);
+              const int64_t total = sink->png  ? uphip_batch_png_sizes(sl->b, sl->jsize.data(), npg)
+                                    : sink->g4 ? uphip_batch_g4_sizes(sl->b, sl->jsize.data(), npg)
+                                               : uphip_batch_jpeg_sizes(sl->b, sl->jsize.data(), npg);
               int64_t o = 0;
               for (int i = 0; i < npg; i++) {
                 sl->joff[(size_t)i] = o;
@@ -1849,8 +1914,10 @@ int uphip_runner_run_host(UphipRunner* r, int64_t njobs, UphipSource* src, Uphip
                 queued = UPH_HIP(hipHostMalloc((void**)&sl->hjpg, cap, hipHostMallocDefault));
                 if (queued) sl->hjpg_cap = cap;
               }
-              queued = queued && (sink->g4 ? uphip_batch_g4_download_async(sl->b, sl->hjpg, (int64_t)sl->hjpg_cap)
-                                           : uphip_batch_jpeg_download_async(sl->b, sl->hjpg, (int64_t)sl->hjpg_cap)) == 0;
+              queued = queued &&
+                       (sink->png  ? uphip_batch_png_download_async(sl->b, sl->hjpg, (int64_t)sl->hjpg_cap)
+                        : sink->g4 ? uphip_batch_g4_download_async(sl->b, sl->hjpg, (int64_t)sl->hjpg_cap)
+                                   : uphip_batch_jpeg_download_async(sl->b, sl->hjpg, (int64_t)sl->hjpg_cap)) == 0;
             } else if (sink->jp2) {
               // the chunk's pages coded on the device; the store tasks write
               queued = jp2_chunk_submit(r, sl, sl->count * oc);
@@ -1895,6 +1962,8 @@ int uphip_runner_run_host(UphipRunner* r, int64_t njobs, UphipSource* src, Uphip
                 else if (sink->g4)
                   store_g4_sheet(r, sink, dc.device, sl->b, sl->first + s, s, sl->hjpg, sl->jsize, sl->joff,
                                  &good);
+                else if (sink->png)
+                  store_png_sheet(r, sink, sl->first + s, s, sl->hjpg, sl->jsize, sl->joff, &good);
                 else if (sink->jp2)
                   store_jp2_chunk_sheet(r, sink, dc.device, sl, sl->first + s, s, &good);
                 else

@@ -69,6 +69,9 @@ EXPORTED = [
     "uphip_g4_encode_host", "uphip_g4_encode", "uphip_batch_encode_g4_async", "uphip_batch_g4_sizes",
     "uphip_batch_g4_download_async", "uphip_pdf_writer_add_page_g4", "uphip_sink_tiff_g4",
     "uphip_sink_pdf_bilevel", "uphip_tiff_g4_write",
+    "uphip_png_encode_host", "uphip_png_encode", "uphip_png_wrap", "uphip_batch_encode_png_async",
+    "uphip_batch_png_sizes", "uphip_batch_png_download_async", "uphip_pdf_writer_add_page_flate",
+    "uphip_sink_png", "uphip_sink_pdf_lossless",
 ]
 
 
@@ -278,6 +281,19 @@ def load_library(path=LIB_PATH):
         "uphip_tiff_g4_write": (C.c_int, [C.c_char_p, C.c_void_p, C.c_size_t, C.c_int32, C.c_int32,
                                           C.c_int32]),
         "uphip_sink_pdf_bilevel": (C.c_void_p, [C.c_char_p, C.POINTER(A.PdfMetadata), C.c_int32]),
+        "uphip_png_encode_host": (C.c_int64, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                              C.c_int32, C.c_int32, C.c_void_p, C.c_int64]),
+        "uphip_png_encode": (C.c_int64, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                         C.c_int32, C.c_int32, C.c_void_p, C.c_int64]),
+        "uphip_png_wrap": (C.c_int64, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                       C.c_void_p, C.c_int64]),
+        "uphip_batch_encode_png_async": (C.c_int, [C.c_void_p]),
+        "uphip_batch_png_sizes": (C.c_int64, [C.c_void_p, C.POINTER(C.c_int64), C.c_int32]),
+        "uphip_batch_png_download_async": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
+        "uphip_pdf_writer_add_page_flate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t,
+                                                      C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+        "uphip_sink_png": (C.c_void_p, [C.c_char_p, C.c_int64, C.c_int32]),
+        "uphip_sink_pdf_lossless": (C.c_void_p, [C.c_char_p, C.POINTER(A.PdfMetadata), C.c_int32]),
     }
     for name, (res, args) in sig.items():
         if not hasattr(L, name):

@@ -195,6 +195,13 @@ class PdfWriter:
         self._call(load_library().uphip_pdf_writer_add_page_g4(self.handle, data, len(data), width,
                                                                height, dpi), "add_page_g4 failed")
 
+    def add_page_flate(self, data: bytes, width, height, fmt, dpi=0):
+        """A lossless page from the zlib stream of the PNG encoder
+        (png_encode's IDAT payload, Batch.png_files); fmt a UPHIP_FMT_* pixel
+        format other than Y400A."""
+        self._call(load_library().uphip_pdf_writer_add_page_flate(self.handle, data, len(data), width,
+                                                                  height, fmt, dpi), "add_page_flate failed")
+
     def add_page_pixels(self, pixels, width, height, stride, fmt, dpi=0):
         """pixels: a contiguous uint8 numpy array, rows `stride` bytes apart;
         fmt PIXEL_GRAY8 or PIXEL_RGB24."""

@@ -170,6 +170,35 @@ class Batch:
                 out.append(None)
         return out
 
+    def encode_png(self):
+        """Queue the lossless output branch on the last run's pages: the zlib
+        streams of PNG IDAT chunks (uphip_batch_encode_png_async; any output
+        format)."""
+        if self.lib.uphip_batch_encode_png_async(self.handle) != 0:
+            _check(self.lib)
+            raise UnpaperHipError("batch_encode_png failed")
+
+    def png_files(self, pages):
+        """The zlib streams of the last encode_png, one per output page
+        (png_wrap makes a file of one, PdfWriter.add_page_flate a PDF page)."""
+        L = self.lib
+        self.wait()
+        sizes = (C.c_int64 * pages)()
+        total = L.uphip_batch_png_sizes(self.handle, sizes, pages)
+        _check(L)
+        if total <= 0:
+            raise UnpaperHipError("batch_png_sizes failed")
+        buf = np.zeros(total, np.uint8)
+        if L.uphip_batch_png_download_async(self.handle, buf.ctypes.data, total) != 0:
+            _check(L)
+            raise UnpaperHipError("batch_png_download failed")
+        self.wait()
+        out, off = [], 0
+        for i in range(pages):
+            out.append(buf[off:off + sizes[i]].tobytes())
+            off += sizes[i]
+        return out
+
     def output_ptr(self, sheet):
         """(device pointer, pitch) of output sheet `sheet` (waits for the run)."""
         pitch = C.c_int64()
@@ -490,6 +519,73 @@ def sink_pdf_bilevel(path, meta=None, dpi=0):
     if not h:
         raise UnpaperHipError("sink_pdf_bilevel failed")
     return _PdfSink(h, L.uphip_sink_destroy, (m, keep))
+
+
+def sink_png(pattern, wrap=0, dpi=0):
+    """One lossless PNG per output page, coded on the device (uphip_sink_png;
+    any output format; dpi > 0 writes a pHYs chunk)."""
+    L = load_library()
+    h = L.uphip_sink_png(pattern.encode(), wrap, dpi)
+    _check(L)
+    if not h:
+        raise UnpaperHipError("sink_png failed")
+    return _Handle(h, L.uphip_sink_destroy)
+
+
+def sink_pdf_lossless(path, meta=None, dpi=0):
+    """All output pages into one PDF of lossless /FlateDecode images coded on
+    the device (uphip_sink_pdf_lossless; not Y400A; dpi 0 = 300).  Call
+    finish() after the run."""
+    from .pdf import _meta_struct
+    L = load_library()
+    m, keep = _meta_struct(meta)
+    h = L.uphip_sink_pdf_lossless(path.encode(), C.byref(m) if m is not None else None, dpi)
+    _check(L)
+    if not h:
+        raise UnpaperHipError("sink_pdf_lossless failed")
+    return _PdfSink(h, L.uphip_sink_destroy, (m, keep))
+
+
+def _png(fn, ptr, pitch, offset, width, height, fmt, dpi):
+    L = load_library()
+    n = fn(ptr, pitch, offset, width, height, fmt, dpi, None, 0)
+    _check(L)
+    if n <= 0:
+        raise UnpaperHipError("png encode failed")
+    buf = np.zeros(n, np.uint8)
+    m = fn(ptr, pitch, offset, width, height, fmt, dpi, buf.ctypes.data, n)
+    _check(L)
+    if m != n:
+        raise UnpaperHipError("png encode: size changed between calls")
+    return buf.tobytes()
+
+
+def png_encode(device_ptr, pitch, width, height, fmt, offset=0, dpi=0):
+    """uphip_png_encode: rows in device memory -> a lossless PNG file (`offset`:
+    the bit of a row that holds pixel 0, bilevel formats only)."""
+    return _png(load_library().uphip_png_encode, device_ptr, pitch, offset, width, height, fmt, dpi)
+
+
+def png_encode_host(rows, width, fmt, offset=0, dpi=0):
+    """uphip_png_encode_host: a 2-D uint8 array of rows (no device); the same
+    bytes as png_encode."""
+    rows = np.ascontiguousarray(rows, np.uint8)
+    return _png(load_library().uphip_png_encode_host, rows.ctypes.data, rows.shape[1], offset, width,
+                rows.shape[0], fmt, dpi)
+
+
+def png_wrap(stream: bytes, width, height, fmt, dpi=0):
+    """uphip_png_wrap: a zlib stream of the encoder as a PNG file."""
+    L = load_library()
+    n = L.uphip_png_wrap(stream, len(stream), width, height, fmt, dpi, None, 0)
+    _check(L)
+    if n <= 0:
+        raise UnpaperHipError("png_wrap failed")
+    buf = np.zeros(n, np.uint8)
+    if L.uphip_png_wrap(stream, len(stream), width, height, fmt, dpi, buf.ctypes.data, n) != n:
+        _check(L)
+        raise UnpaperHipError("png_wrap failed")
+    return buf.tobytes()
 
 
 def _g4(fn, ptr, pitch, bit_offset, width, height):
