@@ -1,6 +1,7 @@
 // kernels_noise.hip — the noisefilter for gfx950 (the split into a parallel
 // pass and an exact resolution: see kernels_gray.hip).
 #include "filters_common.h"
+#include "noise_planes.h"
 
 namespace uph {
 
@@ -20,18 +21,15 @@ namespace uph {
 //     * everything else (edge zone, clustered small components) is replayed
 //       literally, in raster order, by one wave per sheet.
 //   The parallel path is used for N <= 4 (radius constants below).
+//   Y400A and RGB24 classify in tiles staged from the bytes
+//   (k_noise_classify); GRAY8 classifies its dark bit-plane in two streaming
+//   passes (k_noise_cand, k_noise_verdict: noise_planes.h).
 // =========================================================================
-constexpr int kNT = 64;                    // tile height (and width for byte planes)
+constexpr int kNT = 64;                    // tile height and width
 constexpr int kHalo = 14;                  // 4 (ring) + 7 (cluster) + 3 (component)
-constexpr int kRW = kNT + 2 * kHalo;       // 92 region rows
-// GRAY8 tiles are 100 wide: their region rows (from the bit-plane) fill the
-// 128-bit row tables, so the per-row phases cover 100 interior columns
-// instead of 64 for the same work (halo share 2.07 -> 1.84)
-constexpr int kNTG = 100;
-template <int FMT>
-constexpr int noise_tile_w() { return FMT == F_GRAY8 ? kNTG : kNT; }
-constexpr int kZone = 32;                  // sequential edge zone (x or y < 32)
-constexpr int kEligible = kZone + 8;       // parallel only for components at >= 40
+constexpr int kRW = kNT + 2 * kHalo;       // 92 region rows and columns
+constexpr int kZone = kNpZone;             // sequential edge zone (x or y < 32)
+constexpr int kEligible = kNpEligible;     // parallel only for components at >= 40
 
 bool noise_geometry(int32_t W, int32_t H, uint64_t intensity, uint8_t white, NoiseGeom* g) {
   g->W = W;
@@ -70,13 +68,15 @@ constexpr int kCapPerThread = 16;
 static int group_threads(int32_t W, int32_t H) { return (int64_t)W * H > (16 << 20) ? 1024 : 256; }
 size_t noise_scratch_bytes(const NoiseGeom& g) {
   // lists + a global sort buffer for the rare > 8192-trigger sequential case;
-  // the GRAY8 dark bit-plane shares the sort buffer's space (it is read by
-  // k_noise_classify only, before k_noise_group may sort)
+  // the GRAY8 dark bit-plane and, behind it, the small bit-plane share the
+  // sort buffer's space (they are read by k_noise_cand / k_noise_verdict
+  // only, before k_noise_group may sort; narrow tall images need more for
+  // the two planes than for the sort)
   // (and k_noise_group's keys / roots / last, 3 x its LDS cap words)
   size_t sort = 4 * pow2_at_least((size_t)g.capacity);
   const size_t cap3 = 12 * (size_t)kCapPerThread * (size_t)group_threads(g.W, g.H);
   if (sort < cap3) sort = cap3;
-  const size_t bits = 4 * (size_t)noise_bit_words(g) * (size_t)g.H;
+  const size_t bits = 2 * 4 * (size_t)noise_bit_words(g) * (size_t)g.H;
   return noise_list_bytes(g) + (sort > bits ? sort : bits);
 }
 
@@ -169,11 +169,33 @@ __device__ __forceinline__ void wave_append(bool want, int32_t gx, int32_t gy, u
   }
 }
 
+// The same for two lists (a lane wants at most one): both counters' atomics
+// are under way before either answer is waited for.
+__device__ __forceinline__ void wave_append2(bool want1, bool want2, int32_t gx, int32_t gy,
+                                             uint32_t* counter1, uint32_t* list1,
+                                             uint32_t* counter2, uint32_t* list2,
+                                             int32_t capacity) {
+  const unsigned long long M1 = __ballot(want1), M2 = __ballot(want2);
+  if (!(M1 | M2)) return;
+  const int lane = threadIdx.x & 63;
+  uint32_t b1 = 0, b2 = 0;
+  if (lane == 0) {
+    if (M1) b1 = atomicAdd(counter1, (uint32_t)__popcll(M1));
+    if (M2) b2 = atomicAdd(counter2, (uint32_t)__popcll(M2));
+  }
+  b1 = __shfl(b1, 0, 64);
+  b2 = __shfl(b2, 0, 64);
+  const unsigned long long below = (1ull << lane) - 1ull;
+  const uint32_t k = want1 ? b1 + (uint32_t)__popcll(M1 & below) : b2 + (uint32_t)__popcll(M2 & below);
+  if ((want1 | want2) && k < (uint32_t)capacity)
+    (want1 ? list1 : list2)[k] = ((uint32_t)gy << 16) | (uint32_t)gx;
+}
+
 // GRAY8 dark bit-plane: bit b of word w of row y is (pixel 32 w + b < white);
 // columns >= W are 0.  One lane per word, two 16-byte loads (rows are
-// 256-byte pitched, so a row's last word reads inside the pitch).  The
-// classify tiles then read 92-bit region rows as five words each instead of
-// re-reading and re-comparing 2x-overlapping byte halos.
+// 256-byte pitched, so a row's last word reads inside the pitch).  For a
+// plane filtered on its own; in the pipeline the decode hands the plane on
+// (SheetBits::nbits).
 __global__ void __launch_bounds__(256) k_noise_bits(PlaneRef img, NoiseGeom g, uint32_t* bits,
                                                     int64_t bstride, int32_t nwr, float rnwr) {
   const int s = blockIdx.y;
@@ -315,12 +337,12 @@ constexpr int kListCap = 1024;  // LDS work list of one tile (else: row loops)
 #endif
 template <int FMT>
 __global__ void __launch_bounds__(256, UPH_CLASSIFY_OCC) k_noise_classify(PlaneRef img, NoiseGeom g, uint8_t* scratch,
-                                                        int64_t sstride, SheetCtl* ctl,
-                                                        const uint32_t* bits, int64_t bstride) {
+                                                        int64_t sstride, SheetCtl* ctl) {
+  static_assert(FMT != F_GRAY8, "GRAY8 classifies its bit-plane: k_noise_cand, k_noise_verdict");
   // XCD-aware tile order: neighbouring tiles' halos are fetched into one L2
   int bxi, byi, s;
   xcd_block(&bxi, &byi, &s);
-  constexpr int NTX = noise_tile_w<FMT>();  // tile width
+  constexpr int NTX = kNT;                   // tile width
   constexpr int RWX = NTX + 2 * kHalo;       // region columns (<= 128)
   static_assert(RWX > 64 && RWX <= 128, "region rows are two 64-bit halves");
   const int32_t tx0 = bxi * NTX, ty0 = byi * kNT;
@@ -330,8 +352,7 @@ __global__ void __launch_bounds__(256, UPH_CLASSIFY_OCC) k_noise_classify(PlaneR
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   // Everything is kept as 128-bit region rows (bit = region column):
   //   drow dark (lightness < white), trow trigger (max < white; the same
-  //   bits for gray planes), srow small (component <= 4 pixels)
-  constexpr bool kGray = FMT == F_GRAY8;
+  //   bits for Y400A), srow small (component <= 4 pixels)
   constexpr bool kSplit = FMT == F_RGB24;
   // interior columns [kHalo, kHalo + NTX) of a region row's halves
   constexpr uint64_t kIn0 = ~0ull << kHalo;
@@ -344,50 +365,14 @@ __global__ void __launch_bounds__(256, UPH_CLASSIFY_OCC) k_noise_classify(PlaneR
   __shared__ uint32_t crec[kListCap];  // the candidates' components (pack_comp)
   __shared__ int32_t any_dark, nwl;
   uint32_t (*trow)[4] = kSplit ? trow_s : drow;
-  constexpr int B = FMT == F_GRAY8 ? 1 : FMT == F_Y400A ? 2 : 3;
+  constexpr int B = FMT == F_Y400A ? 2 : 3;
   const int64_t pitch = img.P.pitch;
   if (threadIdx.x == 0) {
     any_dark = 0;
     nwl = 0;
   }
   for (int i = threadIdx.x; i < kRW * 4; i += 256) (&srow[0][0])[i] = 0;
-  if constexpr (kGray) {
-    // Region rows from the dark bit-plane (k_noise_bits): row ry is bits
-    // [ox, ox + RWX) of plane row oy + ry, five words realigned by ox mod 32;
-    // words outside the row or the image read as 0
-    bool dark_here = false;
-    if (threadIdx.x < kRW) {
-      const int ry = threadIdx.x;
-      const int32_t gy = oy + ry;
-      const int32_t nwr = (g.W + 31) >> 5;
-      const int32_t wb = ox >> 5;  // floor(ox / 32) (arithmetic shift)
-      const int sh = ox & 31;
-      uint32_t q[5] = {0u, 0u, 0u, 0u, 0u};
-      if (gy >= 0 && gy < g.H) {
-        const uint32_t* row = bits + s * bstride + (int64_t)gy * nwr;
-#pragma unroll
-        for (int j = 0; j < 5; j++)
-          if (wb + j >= 0 && wb + j < nwr) q[j] = row[wb + j];
-      }
-      uint32_t d[4];
-#pragma unroll
-      for (int j = 0; j < 4; j++) d[j] = __builtin_amdgcn_alignbit(q[j + 1], q[j], sh);
-      if (RWX < 128) {  // region columns >= RWX
-        if (RWX <= 96) {
-          d[2] &= RWX > 64 ? (1u << (RWX - 64)) - 1u : 0u;
-          d[3] = 0u;
-        } else {
-          d[3] &= (1u << (RWX - 96)) - 1u;
-        }
-      }
-#pragma unroll
-      for (int j = 0; j < 4; j++) drow[ry][j] = d[j];
-      const uint64_t lo64 = ((uint64_t)d[1] << 32) | d[0], hi64 = ((uint64_t)d[3] << 32) | d[2];
-      dark_here = ry >= kHalo && ry < kHalo + kNT && ((lo64 & kIn0) | (hi64 & kIn1));
-    }
-    __syncthreads();  // any_dark's reset (thread 0, above) lands first
-    if (dark_here) any_dark = 1;
-  } else {
+  {
     // Stage the region rows into LDS with 16-byte loads, all issued before
     // any is consumed.  Rows start 256-byte aligned, so every vector lies
     // inside its row's pitch; out-of-image pixels are masked below.
@@ -669,6 +654,172 @@ __global__ void __launch_bounds__(256, UPH_CLASSIFY_OCC) k_noise_classify(PlaneR
         wave_append(v.clear, gx, gy, NP.nclear, NP.clear, g.capacity);
       }
     }
+  }
+}
+
+// =========================================================================
+// GRAY8 (intensity <= 4 and all_seq alike): the classification as two passes
+// over bit-planes instead of tiles.  Every operator of noise_planes.h is
+// local on the dark bit-plane and reads the true plane (np_word: 0 outside
+// the image, and 0 for a word index outside [0, nwr), never the next row's
+// word), so there is no region whose edge could leave a pixel undecided and
+// the lists hold exactly the tile kernel's sets: the zone pixels, and for
+// every small pixel outside the zone small_verdict_pixels's verdict.
+//   k_noise_cand     a thread takes kPRA rows of one word column (np_strip):
+//                    l3, candidates and zone pixels at full waves with no
+//                    halo; the block's candidate and zone bits are compacted
+//                    into an LDS list (drained in rounds of kPList, so any
+//                    density works with no capacity of its own), one flood
+//                    or one seq entry a lane; every word of the small plane
+//                    is then written once by its owner
+//   k_noise_verdict  the same mapping over the complete small plane: the
+//                    small pixels at x, y >= 32 compacted likewise, one
+//                    np_verdict a lane
+// The lists only fail where they did: past g.capacity (k_noise_apply,
+// k_noise_group).
+// =========================================================================
+// rows a thread (4, 8, 16, 32 measured: within 10 % of each other, both
+// kernels are bound by the scattered box reads, not by their blocks)
+constexpr int kPRA = 16;            // k_noise_cand
+constexpr int kPRB = 16;            // k_noise_verdict
+constexpr int kPList = 1024;        // LDS list entries a round
+// entry: bit | thread << 5 | row << 13 | kind << 18
+constexpr uint32_t kPZone = 1u << 18;
+
+struct PlaneThread {
+  int32_t wi, y0;  // word column, first row; y0 >= H: no words
+};
+// thread t of the sheet's flattened (strip, word) grid; t / nwr from the
+// float reciprocal, corrected by one either way
+template <int R>
+__device__ __forceinline__ PlaneThread plane_thread(int32_t t, int32_t nwr, float rnwr) {
+  int32_t q = (int32_t)((float)t * rnwr);
+  if (q * nwr > t) q--;
+  else if ((q + 1) * nwr <= t) q++;
+  return PlaneThread{t - q * nwr, q * R};
+}
+
+// Appends the set bits of m (row r of this thread) to the block's list while
+// it has room; returns the bits left for the next round.
+__device__ __forceinline__ uint32_t list_append(uint32_t m, int r, uint32_t kind, int32_t* nwl,
+                                                uint32_t* wl) {
+  if (!m) return 0u;
+  int k = atomicAdd(nwl, __popc(m));
+  while (m && k < kPList) {
+    const int b = __ffs(m) - 1;
+    m &= m - 1;
+    wl[k++] = (uint32_t)b | (threadIdx.x << 5) | ((uint32_t)r << 13) | kind;
+  }
+  return m;
+}
+
+__global__ void __launch_bounds__(256) k_noise_cand(NoiseGeom g, uint8_t* scratch, int64_t sstride,
+                                                    const uint32_t* bits, int64_t bstride,
+                                                    uint32_t* small, int64_t small_stride,
+                                                    int32_t nwr, float rnwr) {
+  const int s = blockIdx.y;
+  const NpPlane P{bits + s * bstride, nwr, g.H};
+  NoisePtrs NP = noise_ptrs(g, scratch + s * sstride);
+  const int32_t t0 = blockIdx.x * 256;
+  const PlaneThread me = plane_thread<kPRA>(t0 + threadIdx.x, nwr, rnwr);
+  __shared__ uint32_t smallw[kPRA][256];
+  __shared__ uint32_t wl[kPList];
+  __shared__ int32_t nwl;
+  uint32_t cand[kPRA], zone[kPRA];
+  {
+    uint32_t l3[kPRA];
+    if (me.y0 < g.H) {
+      np_strip<kPRA>(P, me.wi, me.y0, g.all_seq, l3, cand, zone);
+    } else {
+#pragma unroll
+      for (int r = 0; r < kPRA; r++) cand[r] = zone[r] = 0u;
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < kPRA; r++) {
+    smallw[r][threadIdx.x] = 0u;
+    if (g.all_seq) cand[r] = 0u;  // nothing is judged
+  }
+  for (;;) {
+    if (threadIdx.x == 0) nwl = 0;
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < kPRA; r++) {
+      cand[r] = list_append(cand[r], r, 0u, &nwl, wl);
+      zone[r] = list_append(zone[r], r, kPZone, &nwl, wl);
+    }
+    __syncthreads();
+    const int tot = nwl, n = imin(tot, kPList);
+    for (int b0 = 0; b0 < n; b0 += 256) {  // uniform trip count
+      const int i = b0 + threadIdx.x;
+      bool seq = false;
+      int32_t gx = 0, gy = 0;
+      if (i < n) {
+        const uint32_t e = wl[i];
+        const int et = (e >> 5) & 255, r = (e >> 13) & 31;
+        const PlaneThread o = plane_thread<kPRA>(t0 + et, nwr, rnwr);
+        gx = 32 * o.wi + (int32_t)(e & 31u);
+        gy = o.y0 + r;
+        seq = e & kPZone;
+        if (!seq) {
+          uint32_t comp[9], D[9];
+          if (np_flood9(P, gx, gy, comp, D) <= kNpSmallMax) atomicOr(&smallw[r][et], 1u << (e & 31u));
+        }
+      }
+      wave_append(seq, gx, gy, NP.nseq, NP.seq, g.capacity);
+    }
+    __syncthreads();  // the floods' bits landed; nwl may be reset
+    if (tot <= kPList) break;
+  }
+  if (g.all_seq || me.y0 >= g.H) return;
+  uint32_t* out = small + s * small_stride + (int64_t)me.y0 * nwr + me.wi;
+#pragma unroll
+  for (int r = 0; r < kPRA; r++)
+    if (me.y0 + r < g.H) out[(int64_t)r * nwr] = smallw[r][threadIdx.x];
+}
+
+__global__ void __launch_bounds__(256) k_noise_verdict(NoiseGeom g, uint8_t* scratch,
+                                                       int64_t sstride, const uint32_t* bits,
+                                                       int64_t bstride, const uint32_t* small,
+                                                       int64_t small_stride, int32_t nwr,
+                                                       float rnwr) {
+  const int s = blockIdx.y;
+  const NpPlane P{bits + s * bstride, nwr, g.H};
+  const NpPlane S{small + s * small_stride, nwr, g.H};
+  NoisePtrs NP = noise_ptrs(g, scratch + s * sstride);
+  const int32_t t0 = blockIdx.x * 256;
+  const PlaneThread me = plane_thread<kPRB>(t0 + threadIdx.x, nwr, rnwr);
+  __shared__ uint32_t wl[kPList];
+  __shared__ int32_t nwl;
+  uint32_t todo[kPRB];  // the thread's small pixels outside the zone
+#pragma unroll
+  for (int r = 0; r < kPRB; r++) {
+    const int32_t y = me.y0 + r;
+    todo[r] = me.wi > 0 && y >= kNpZone && y < g.H ? S.w[(int64_t)y * nwr + me.wi] : 0u;
+  }
+  for (;;) {
+    if (threadIdx.x == 0) nwl = 0;
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < kPRB; r++) todo[r] = list_append(todo[r], r, 0u, &nwl, wl);
+    __syncthreads();
+    const int tot = nwl, n = imin(tot, kPList);
+    for (int b0 = 0; b0 < n; b0 += 256) {  // uniform trip count
+      const int i = b0 + threadIdx.x;
+      int v = NP_NONE;
+      int32_t gx = 0, gy = 0;
+      if (i < n) {
+        const uint32_t e = wl[i];
+        const PlaneThread o = plane_thread<kPRB>(t0 + (int)((e >> 5) & 255), nwr, rnwr);
+        gx = 32 * o.wi + (int32_t)(e & 31u);
+        gy = o.y0 + (int)((e >> 13) & 31);
+        v = np_verdict(P, S, gx, gy, g.intensity);
+      }
+      wave_append2(v == NP_SEQ, v == NP_CLEAR, gx, gy, NP.nseq, NP.seq, NP.nclear, NP.clear,
+                   g.capacity);
+    }
+    __syncthreads();  // nwl may be reset
+    if (tot <= kPList) break;
   }
 }
 
@@ -1389,25 +1540,38 @@ template <int FMT>
 static void launch_noise_t(const PlaneRef& img, const NoiseGeom& g, uint8_t* scr, int64_t ss,
                            SheetCtl* ctl, int count, hipStream_t st, uint32_t* sortbuf,
                            int64_t sort_stride, const SheetBits& ready) {
-  constexpr int ntx = noise_tile_w<FMT>();
-  dim3 grid((g.W + ntx - 1) / ntx, (g.H + kNT - 1) / kNT, count);
   NoiseGeom gd = g;  // the kernels' copy
   gd.diag = diag_noise();
   gd.bbits = ready.bbits;
   gd.bb_stride = ready.stride;
-  uint32_t* bits = ready.nbits;
-  int64_t bstride = ready.stride;
-  if (FMT == F_GRAY8 && !bits) {
-    // the dark bit-plane in the sort buffer's space (noise_scratch_bytes)
+  if constexpr (FMT == F_GRAY8) {
+    // the dark bit-plane from the decode, or made here at the start of the
+    // sort buffer's space; the small bit-plane in that space too, behind it
+    // (noise_scratch_bytes)
     const int32_t nwr = noise_bit_words(g);
-    bits = sortbuf;
-    bstride = sort_stride;
     const int64_t words = (int64_t)nwr * g.H;
-    hipLaunchKernelGGL(k_noise_bits, dim3((unsigned)((words + 255) / 256), count), dim3(256), 0, st,
-                       img, g, bits, bstride, nwr, 1.0f / (float)nwr);
+    const uint32_t* bits = ready.nbits;
+    int64_t bstride = ready.stride;
+    uint32_t* small = sortbuf;
+    if (!bits) {
+      hipLaunchKernelGGL(k_noise_bits, dim3((unsigned)((words + 255) / 256), count), dim3(256), 0, st,
+                         img, g, sortbuf, sort_stride, nwr, 1.0f / (float)nwr);
+      bits = sortbuf;
+      bstride = sort_stride;
+      small = sortbuf + words;
+    }
+    const int64_t ta = (int64_t)nwr * ((g.H + kPRA - 1) / kPRA);
+    const int64_t tb = (int64_t)nwr * ((g.H + kPRB - 1) / kPRB);
+    const dim3 grid((unsigned)((ta + 255) / 256), count), gridb((unsigned)((tb + 255) / 256), count);
+    UPH_LAUNCH_DIAG(131072, k_noise_cand, grid, dim3(256), 0, st, gd, scr, ss, bits, bstride, small,
+                    sort_stride, nwr, 1.0f / (float)nwr);
+    if (!g.all_seq)
+      UPH_LAUNCH_DIAG(131072, k_noise_verdict, gridb, dim3(256), 0, st, gd, scr, ss, bits, bstride,
+                      small, sort_stride, nwr, 1.0f / (float)nwr);
+  } else {
+    dim3 grid((g.W + kNT - 1) / kNT, (g.H + kNT - 1) / kNT, count);
+    UPH_LAUNCH_DIAG(131072, k_noise_classify<FMT>, grid, dim3(256), 0, st, img, gd, scr, ss, ctl);
   }
-  UPH_LAUNCH_DIAG(131072, k_noise_classify<FMT>, grid, dim3(256), 0, st, img, gd, scr, ss, ctl,
-                     bits, bstride);
   hipLaunchKernelGGL(k_noise_apply<FMT>, dim3(64, count), dim3(256), 0, st, img, gd, scr, ss, ctl);
   const int gt = group_threads(g.W, g.H);
   if (!(diag_skip() & 2)) {
