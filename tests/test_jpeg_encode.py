@@ -384,6 +384,33 @@ def test_runner_jpeg_sink_many_pages(hip, oracle, tmp_path):
         assert got == pil_encode(sheet.to_gray(), 75, 0), i
 
 
+@pytest.mark.gpu
+def test_runner_jpeg_sink_overflow_reencodes(hip, oracle, tmp_path):
+    """The runner's side of test_batch_encode_overflow_reencodes: noise at
+    quality 100 outgrows its share of the batch's encode buffer, so chunk 0
+    (noise, noise) comes back with every page -1 -- nothing to download, on a
+    slot whose packed buffer was never allocated -- and both pages are encoded
+    again singly; chunk 1 (text) takes the ordinary packed path.  Every file
+    equals PIL's encode of its page (no processing: the sheet is the page)."""
+    from unpaper_hip.pipeline import Runner, sink_jpeg, source_memory
+    w, h = 640, 480
+    opts = oracle.default_options()
+    opts.disable = A.NO_PROCESSING
+    rng = np.random.default_rng(5)
+    pages = [rng.integers(0, 256, (h, w)).astype(np.uint8) for _ in range(2)]
+    pages.append(content("text", w, h)[..., 0].copy())
+    stack = np.stack(pages)
+    r = Runner(opts, 2, w, h, A.FMT_GRAY8, devices=(0,), streams=1, host_threads=2)
+    try:
+        failed, err = r.run_host(3, source_memory(stack.ctypes.data, w, w * h, 3, keep=stack),
+                                 sink_jpeg(str(tmp_path / "p_%d.jpg"), 0, 100, 0))
+        assert failed == 0, err
+    finally:
+        r.close()
+    for i, page in enumerate(pages):
+        assert open(tmp_path / ("p_%d.jpg" % i), "rb").read() == pil_encode(page, 100, 0), i
+
+
 def test_sink_jpeg_argument_checks():
     from unpaper_hip.device import load_library
     L = load_library()

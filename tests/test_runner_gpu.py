@@ -435,6 +435,24 @@ def test_runner_failed_job_is_isolated(hip, oracle):
     assert not out[4].any()
 
 
+def test_runner_sink_that_cannot_store(hip, oracle, tmp_path):
+    """A sink whose files cannot be created (a pattern inside a directory
+    that does not exist): every sheet runs and then fails at its store (the
+    job is marked failed as in batch_worker.c:214-231), none is counted done."""
+    w, h = SMALL
+    n = 3
+    opts = oracle.default_options()
+    host_in = np.stack([p.payload() for p in _pages(n, 95, w, h)])
+    r = Runner(opts, 2, w, h, A.FMT_GRAY8, devices=(0,), streams=2, host_threads=2)
+    try:
+        failed, err = r.run_host(n, source_memory(host_in.ctypes.data, w, w * h, n, keep=host_in),
+                                 sink_pnm(str(tmp_path / "no_such_dir" / "out_%d.pgm")))
+        assert failed == 3 and "could not be stored" in err, (failed, err)
+        assert r.stats().jobs_done == 0
+    finally:
+        r.close()
+
+
 def test_runner_two_threads_one_device(hip, oracle):
     """Two runner device threads bound to the same GPU (the multi-device
     fan-out path): disjoint device-resident shards, per-thread batches."""

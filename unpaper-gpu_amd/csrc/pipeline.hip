@@ -547,6 +547,35 @@ void flip_all(UphipBatch* b, int count) {
   hipLaunchKernelGGL(k_flip_all, dim3((count + 255) / 256), dim3(256), 0, b->st, b->ctl, count);
 }
 
+int out_pages(const UphipBatch* b) { return b->o.output_count < 1 ? 1 : b->o.output_count; }
+
+// The pages' sizes of a finished packed encode (`what`: jpeg, g4, png), read
+// from the encoder's pinned `host_sizes`: each into `sizes` (-1: the page
+// outgrew its share of the buffer), their total returned.  A codec without a
+// single-page re-encode (missing_ok false) refuses a page without a size.
+int64_t packed_sizes(UphipBatch* b, const int64_t* host_sizes, int npages, bool missing_ok, const char* what,
+                     int64_t* sizes, int32_t max_pages) {
+  if (!host_sizes || npages <= 0) return fail("batch_%s_sizes: no encode", what), -1;
+  if (uphip_batch_query(b) != 1) return fail("batch_%s_sizes: the encode has not finished", what), -1;
+  int64_t total = 0;
+  for (int i = 0; i < npages; i++) {
+    const int64_t s = host_sizes[i];
+    if (s <= 0 && !missing_ok) return fail("batch_%s_sizes: page %d has no size", what, i), -1;
+    if (sizes && i < max_pages) sizes[i] = s < 0 ? -1 : s;
+    if (s > 0) total += s;
+  }
+  return total;
+}
+
+// Queue the copy of the `total` packed bytes at `out` into the caller's buffer.
+int packed_download(UphipBatch* b, int64_t total, const uint8_t* out, void* host, int64_t capacity,
+                    const char* what) {
+  if (total == 0) return 0;  // every page came back -1: nothing to copy
+  if (!host || capacity < total) return fail("batch_%s_download: buffer too small", what), -1;
+  hipSetDevice(b->device);
+  return UPH_HIP(hipMemcpyAsync(host, out, (size_t)total, hipMemcpyDeviceToHost, b->st)) ? 0 : -1;
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------
@@ -1796,7 +1825,7 @@ int uphip_batch_encode_jpeg_async(UphipBatch* b, int32_t quality, int32_t sampli
   if (!b || b->last_count <= 0) return fail("batch_encode_jpeg: nothing to encode"), -1;
   if (quality == 0) quality = UPHIP_JPEG_DEFAULT_QUALITY;
   hipSetDevice(b->device);
-  const int oc = b->o.output_count < 1 ? 1 : b->o.output_count;
+  const int oc = out_pages(b);
   const int n = b->last_count * oc;
   const int bpp = b->work_fmt == F_GRAY8 ? 1 : 3;
   const int32_t pw = b->out_w / oc;
@@ -1817,31 +1846,18 @@ int uphip_batch_encode_jpeg_async(UphipBatch* b, int32_t quality, int32_t sampli
 }
 
 int64_t uphip_batch_jpeg_sizes(UphipBatch* b, int64_t* sizes, int32_t max_pages) {
-  if (!b || !b->jenc || b->jenc_pages <= 0) return fail("batch_jpeg_sizes: no encode"), -1;
-  if (uphip_batch_query(b) != 1) return fail("batch_jpeg_sizes: the encode has not finished"), -1;
-  int64_t total = 0;
-  for (int i = 0; i < b->jenc_pages; i++) {
-    const int64_t s = b->jenc->host_sizes[i];
-    if (sizes && i < max_pages) sizes[i] = s < 0 ? -1 : s;
-    if (s > 0) total += s;
-  }
-  return total;
+  return packed_sizes(b, b && b->jenc ? b->jenc->host_sizes : nullptr, b ? b->jenc_pages : 0, true, "jpeg", sizes,
+                      max_pages);
 }
 
 int uphip_batch_jpeg_download_async(UphipBatch* b, void* host, int64_t capacity) {
   const int64_t total = uphip_batch_jpeg_sizes(b, nullptr, 0);
-  if (total < 0) return -1;
-  if (!host || capacity < total) return fail("batch_jpeg_download: buffer too small"), -1;
-  if (total == 0) return 0;
-  hipSetDevice(b->device);
-  return UPH_HIP(hipMemcpyAsync(host, b->jenc->out, (size_t)total, hipMemcpyDeviceToHost, b->st))
-             ? 0
-             : -1;
+  return total < 0 ? -1 : packed_download(b, total, b->jenc->out, host, capacity, "jpeg");
 }
 
 int uphip_batch_jpeg_page(UphipBatch* b, int32_t page, const void** device_src, int64_t* pitch,
                           int32_t* width, int32_t* height, int32_t* format) {
-  const int oc = b && b->o.output_count > 1 ? b->o.output_count : 1;
+  const int oc = b ? out_pages(b) : 1;
   if (!b || page < 0 || page >= b->last_count * oc) return fail("batch_jpeg_page: bad page"), -1;
   hipSetDevice(b->device);
   if (!UPH_HIP(hipStreamSynchronize(b->st))) return -1;
@@ -1866,7 +1882,7 @@ int uphip_batch_encode_g4_async(UphipBatch* b) {
     return fail("batch_encode_g4: the batch's output format is %d, Group 4 codes bilevel (MONOWHITE) "
                 "sheets only", b->out_fmt), -1;
   hipSetDevice(b->device);
-  const int oc = b->o.output_count < 1 ? 1 : b->o.output_count;
+  const int oc = out_pages(b);
   const int32_t pw = b->out_w / oc;
   if (pw <= 0) return fail("batch_encode_g4: empty pages"), -1;
   // a page's share of the packed buffer: its packed rows + 1 KiB (text codes
@@ -1880,31 +1896,20 @@ int uphip_batch_encode_g4_async(UphipBatch* b) {
 }
 
 int64_t uphip_batch_g4_sizes(UphipBatch* b, int64_t* sizes, int32_t max_pages) {
-  if (!b || !b->g4 || b->g4_pages <= 0) return fail("batch_g4_sizes: no encode"), -1;
-  if (uphip_batch_query(b) != 1) return fail("batch_g4_sizes: the encode has not finished"), -1;
-  int64_t total = 0;
-  for (int i = 0; i < b->g4_pages; i++) {
-    const int64_t s = b->g4->host_sizes[i];
-    if (sizes && i < max_pages) sizes[i] = s < 0 ? -1 : s;
-    if (s > 0) total += s;
-  }
-  return total;
+  return packed_sizes(b, b && b->g4 ? b->g4->host_sizes : nullptr, b ? b->g4_pages : 0, true, "g4", sizes,
+                      max_pages);
 }
 
 int uphip_batch_g4_download_async(UphipBatch* b, void* host, int64_t capacity) {
   const int64_t total = uphip_batch_g4_sizes(b, nullptr, 0);
-  if (total < 0) return -1;
-  if (total == 0) return 0;  // every page came back -1
-  if (!host || capacity < total) return fail("batch_g4_download: buffer too small"), -1;
-  hipSetDevice(b->device);
-  return UPH_HIP(hipMemcpyAsync(host, b->g4->out, (size_t)total, hipMemcpyDeviceToHost, b->st)) ? 0 : -1;
+  return total < 0 ? -1 : packed_download(b, total, b->g4->out, host, capacity, "g4");
 }
 
 // ---- lossless output branch: PNG / Flate (png_enc.h) ----------------------
 int uphip_batch_encode_png_async(UphipBatch* b) {
   if (!b || b->last_count <= 0) return fail("batch_encode_png: nothing to encode"), -1;
   hipSetDevice(b->device);
-  const int oc = b->o.output_count < 1 ? 1 : b->o.output_count;
+  const int oc = out_pages(b);
   const int32_t pw = b->out_w / oc;
   if (pw <= 0) return fail("batch_encode_png: empty pages"), -1;
   if (!b->png) b->png = new PngContext();
@@ -1924,24 +1929,13 @@ int uphip_batch_encode_png_async(UphipBatch* b) {
 }
 
 int64_t uphip_batch_png_sizes(UphipBatch* b, int64_t* sizes, int32_t max_pages) {
-  if (!b || !b->png || b->png_pages <= 0) return fail("batch_png_sizes: no encode"), -1;
-  if (uphip_batch_query(b) != 1) return fail("batch_png_sizes: the encode has not finished"), -1;
-  int64_t total = 0;
-  for (int i = 0; i < b->png_pages; i++) {
-    const int64_t s = b->png->host_sizes[i];
-    if (s <= 0) return fail("batch_png_sizes: page %d has no size", i), -1;
-    if (sizes && i < max_pages) sizes[i] = s;
-    total += s;
-  }
-  return total;
+  return packed_sizes(b, b && b->png ? b->png->host_sizes : nullptr, b ? b->png_pages : 0, false, "png", sizes,
+                      max_pages);
 }
 
 int uphip_batch_png_download_async(UphipBatch* b, void* host, int64_t capacity) {
   const int64_t total = uphip_batch_png_sizes(b, nullptr, 0);
-  if (total < 0) return -1;
-  if (!host || capacity < total) return fail("batch_png_download: buffer too small"), -1;
-  hipSetDevice(b->device);
-  return UPH_HIP(hipMemcpyAsync(host, b->png->out, (size_t)total, hipMemcpyDeviceToHost, b->st)) ? 0 : -1;
+  return total < 0 ? -1 : packed_download(b, total, b->png->out, host, capacity, "png");
 }
 
 int uphip_batch_set_timing(UphipBatch* b, int32_t enable) {

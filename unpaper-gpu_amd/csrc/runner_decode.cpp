@@ -1,0 +1,410 @@
+// runner_decode.cpp — the load side of a host-fed run: a source's page into
+// the slot's staging (the decode queue's work, lib/decode_queue.c), the host
+// half of JPEG / JPEG 2000 / PDF pages, and what the device thread queues for
+// a loaded chunk: the staging upload, the pages' device decode and, for a
+// JPEG 2000 sink, the chunk's device encode.
+#include <algorithm>
+#include <cstdio>
+#include <cstring>
+
+#include "runner_internal.h"
+
+namespace uph {
+namespace {
+
+int mem_load(const UphipSource* s, int64_t idx, void* dst, int64_t linesize,
+             const UphipPnmInfo& geo) {
+  if (idx < 0 || idx >= s->npages) return fail("source_memory: page %lld out of range", (long long)idx), -1;
+  const int64_t rb = row_bytes(geo.width, geo.format);
+  const uint8_t* src = s->base + idx * s->page_stride;
+  uint8_t* d = (uint8_t*)dst;
+  if (linesize == s->linesize && linesize == rb) {
+    memcpy(d, src, (size_t)(rb * geo.height));
+  } else {
+    for (int32_t y = 0; y < geo.height; y++)
+      memcpy(d + (int64_t)y * linesize, src + (int64_t)y * s->linesize, (size_t)rb);
+  }
+  return 0;
+}
+
+int pnm_load(const UphipSource* s, int64_t idx, void* dst, int64_t linesize,
+             const UphipPnmInfo& geo) {
+  if (idx < 0 || idx >= (int64_t)s->paths.size())
+    return fail("source_pnm: page %lld out of range", (long long)idx), -1;
+  return uphip_image_read(s->paths[(size_t)idx].c_str(), dst, linesize, &geo);
+}
+
+// A page of the runner's geometry, or the error that names it.
+bool same_geometry(const UphipRunner* r, const UphipPnmInfo& g, const char* kind, const char* name) {
+  if (g.width == r->geo.page_width && g.height == r->geo.page_height && g.format == r->geo.page_format)
+    return true;
+  return fail("%s: %s is %dx%d format %d, expected %dx%d format %d", kind, name, g.width, g.height, g.format,
+              r->geo.page_width, r->geo.page_height, r->geo.page_format);
+}
+
+bool is_jpeg_file(const std::string& path) {
+  FILE* f = fopen(path.c_str(), "rb");
+  if (!f) return false;
+  uint8_t sig[3];
+  const bool yes = fread(sig, 1, 3, f) == 3 && sig[0] == 0xFF && sig[1] == 0xD8 && sig[2] == 0xFF;
+  fclose(f);
+  return yes;
+}
+
+// The host half of a JPEG page into the slot's pinned buffer `jp`.
+bool jpeg_load_mem(UphipRunner* r, int device, const uint8_t* data, size_t size, const char* name,
+                   JpegPage* jp) {
+  thread_local JdecStreamHost S;
+  // the frame header first: a file of the wrong geometry (or a crafted one
+  // claiming a huge frame) is refused before anything is sized from it
+  UphipPnmInfo info{0, 0, 0};
+  if (!jpeg_probe_mem(data, size, name, &info) || !same_geometry(r, info, "jpeg", name)) return false;
+  // a one-scan sequential file goes to the device as its unstuffed entropy
+  // data (Huffman decoding there too); progressive / multi-scan files are
+  // entropy-decoded here
+  const int dev = jpeg_stream_prepare(data, size, name, &S);
+  if (dev < 0) return false;
+  JpegDecoded d;
+  if (!dev && !jpeg_entropy_decode(data, size, name, &d)) return false;
+  // pinned memory for this device (the pool thread may have another current)
+  if (uphip_set_device(device) != 0) return false;
+  const size_t need = (size_t)(dev ? S.hd.total_bytes : d.h.total_bytes);
+  if (!jp->host.reserve(need, need / 4)) return false;
+  if (dev)
+    jpeg_stream_pack(S, jp->host.as());
+  else
+    jpeg_pack(d, jp->host.as());
+  jp->h = dev ? S.hd.h : d.h;
+  jp->dev = dev == 1;
+  jp->j2k = false;
+  jp->bytes = need;
+  jp->on = true;
+  return true;
+}
+
+bool is_j2k_file(const std::string& path) {
+  FILE* f = fopen(path.c_str(), "rb");
+  if (!f) return false;
+  uint8_t sig[12];
+  const size_t n = fread(sig, 1, 12, f);
+  fclose(f);
+  return j2k::is_j2k(sig, n);
+}
+
+// The host half of a JPEG 2000 page (headers, packet headers) into the
+// slot's pinned buffer `jp`: its code-block jobs, then their codewords.
+bool j2k_load_mem(UphipRunner* r, int device, const uint8_t* data, size_t size, const char* name,
+                  JpegPage* jp) {
+  thread_local j2k::T1Batch tb;
+  UphipPnmInfo info{0, 0, 0};
+  if (!j2k::probe(data, size, name, &info) || !same_geometry(r, info, "jp2", name)) return false;
+  if (!j2k::decode_host(data, size, name, &jp->img, nullptr, &tb)) return false;
+  if (uphip_set_device(device) != 0) return false;
+  jp->njobs = (int32_t)tb.jobs.size();
+  jp->jobs_bytes = (sizeof(j2k::T1Job) * tb.jobs.size() + 255) & ~(size_t)255;
+  jp->maxw = tb.maxw;
+  jp->maxh = tb.maxh;
+  const size_t need = jp->jobs_bytes + tb.data.size();
+  if (!jp->host.reserve(need, need / 4)) return false;
+  memcpy(jp->host.as(), tb.jobs.data(), sizeof(j2k::T1Job) * tb.jobs.size());
+  memcpy(jp->host.as() + jp->jobs_bytes, tb.data.data(), tb.data.size());
+  jp->h = JpegHeader{};
+  jp->h.scratch_bytes = (int64_t)j2k::decode_tmp_bytes(jp->img);  // the line buffer
+  jp->j2k = true;
+  jp->dev = false;
+  jp->bytes = need;
+  jp->on = true;
+  return true;
+}
+
+// A JPEG or JPEG 2000 file through its loader above.
+bool file_load(decltype(jpeg_load_mem)* load, UphipRunner* r, int device, const std::string& path, JpegPage* jp) {
+  // per pool thread, kept across pages: fresh multi-MB buffers per page would
+  // page-fault (and contend on the address space) on every load
+  thread_local std::vector<uint8_t> file;
+  return jpeg_read_file(path.c_str(), &file) && load(r, device, file.data(), file.size(), path.c_str(), jp);
+}
+
+// Page `idx` of a PDF source (the decode queue of the PDF pipeline,
+// pdf_pipeline_cpu_batch.c:381-496): its image's JPEG / JPEG 2000 bytes to
+// the device decode like a file's, Flate / raw pixels decoded here.
+bool pdf_load(UphipRunner* r, int device, const UphipSource* s, int64_t idx, uint8_t* dst, JpegPage* jp) {
+  if (idx < 0 || idx >= s->pdf->page_count())
+    return fail("source_pdf: page %lld out of range (%d pages)", (long long)idx, s->pdf->page_count());
+  thread_local pdf::PageImage im;
+  UphipPnmInfo g{0, 0, 0};
+  if (!pdf::page_geometry(*s->pdf, (int)idx, s->pdf_dpi, &im, &g)) return false;
+  char name[64];
+  snprintf(name, sizeof(name), "pdf page %lld", (long long)idx);
+  if (im.format == pdf::kJpeg) return jpeg_load_mem(r, device, im.data.data(), im.data.size(), name, jp);
+  if (im.format == pdf::kJp2) return j2k_load_mem(r, device, im.data.data(), im.data.size(), name, jp);
+  return same_geometry(r, g, "pdf", name) && pdf::decode_pixels(im, dst, r->in_pitch, name);
+}
+
+size_t up256(size_t n) { return (n + 255) & ~(size_t)255; }
+
+constexpr int kJ2kSubBatch = 16;  // pages coded per k_j2k_t1enc launch (bounds the arena)
+
+}  // namespace
+
+bool load_page(UphipRunner* r, int device, const UphipSource* s, int64_t job, int32_t j,
+               uint8_t* dst, JpegPage* jp) {
+  const UphipPnmInfo geo{r->geo.page_width, r->geo.page_height, r->geo.page_format};
+  const int64_t idx = job * r->opts.input_count + j;
+  if (s->load) return s->load(s->user, job, j, dst, r->in_pitch) == 0;
+  if (s->base) return mem_load(s, idx, dst, r->in_pitch, geo) == 0;
+  if (s->pdf) return pdf_load(r, device, s, idx, dst, jp);
+  if (idx >= 0 && idx < (int64_t)s->paths.size()) {
+    const std::string& path = s->paths[(size_t)idx];
+    if (is_jpeg_file(path)) return file_load(jpeg_load_mem, r, device, path, jp);
+    if (is_j2k_file(path)) return file_load(j2k_load_mem, r, device, path, jp);
+  }
+  return pnm_load(s, idx, dst, r->in_pitch, geo) == 0;
+}
+
+// Queue the H2D copy of the slot's staged pages, skipping the JPEG pages (their
+// decode writes the batch's input slots itself, after this copy): runs of
+// other pages go as one copy each (the staging is laid out like the slots).
+bool upload_staging(UphipRunner* r, Slot* sl, int npages) {
+  bool any = false;
+  for (int p = 0; p < npages; p++) any |= sl->jpg[(size_t)p].on;
+  if (!any)
+    return uphip_batch_upload_async(sl->b, sl->count, sl->hin.as(), r->in_pitch, r->in_page_stride) == 0;
+  hipStream_t st = (hipStream_t)uphip_batch_stream(sl->b);
+  for (int p = 0; p < npages;) {
+    if (sl->jpg[(size_t)p].on) {
+      p++;
+      continue;
+    }
+    int e = p;
+    while (e < npages && !sl->jpg[(size_t)e].on) e++;
+    int64_t pitch = 0;
+    uint8_t* dst = (uint8_t*)uphip_batch_input_ptr(sl->b, p, &pitch);
+    if (!dst || pitch != r->in_pitch ||
+        !UPH_HIP(hipMemcpyAsync(dst, sl->hin.as() + (int64_t)p * r->in_page_stride,
+                                (size_t)((int64_t)(e - p) * r->in_page_stride),
+                                hipMemcpyHostToDevice, st)))
+      return false;
+    p = e;
+  }
+  return true;
+}
+
+// Queue the chunk's JPEG and JPEG 2000 pages on the slot's stream: upload each
+// packed page (JPEG 2000: its coefficient planes), then decode it into its
+// input slot (after the staging upload, before the run).
+bool jpeg_submit(Slot* sl, int npages) {
+  size_t total = 0, scr = 0, pk = 0, hs = 0;
+  int ndev = 0;
+  int64_t max_nsub = 0, max_nmac = 0;
+  sl->jdev = false;
+  for (int p = 0; p < npages; p++) {
+    const JpegPage& jp = sl->jpg[(size_t)p];
+    if (!jp.on) continue;
+    total += up256(jp.bytes);  // page starts aligned (JPEG 2000 planes are int32)
+    scr = std::max(scr, (size_t)jp.h.scratch_bytes);
+    if (jp.dev) {
+      const JdecHeader& hd = *jp.host.as<const JdecHeader>();
+      ndev++;
+      pk += up256((size_t)jp.h.total_bytes);
+      hs += up256(jdec_scratch_bytes(hd));
+      max_nsub = std::max<int64_t>(max_nsub, hd.nsub);
+      max_nmac = std::max<int64_t>(max_nmac, hd.nmac);
+    }
+  }
+  if (!total) return true;
+  // the slot's stream is idle here (the slot was free): old buffers can go
+  auto grow = [](Buffer& b, size_t need) { return b.reserve(need, need / 4); };
+  if (!grow(sl->djpg, total) || (scr && !grow(sl->dscr, scr))) return false;
+  uint8_t* const djpg = sl->djpg.as();
+  uint8_t* const dscr = sl->dscr.as();
+  hipStream_t st = (hipStream_t)uphip_batch_stream(sl->b);
+  if (ndev) {
+    sl->jdev = true;
+    if (!grow(sl->djpk, pk) || !grow(sl->djsc, hs) || !grow(sl->djst, 4 * (size_t)npages) ||
+        !sl->djob.reserve(sizeof(JdecJob) * (size_t)npages) || !sl->hjob.reserve(sizeof(JdecJob) * (size_t)npages) ||
+        !UPH_HIP(hipMemsetAsync(sl->djst.as(), 0, 4 * (size_t)npages, st)))
+      return false;
+  }
+  JdecJob* const hjob = sl->hjob.as<JdecJob>();
+  // upload every page; the device-decoded ones as one batch of jobs
+  size_t off = 0, poff = 0, soff = 0;
+  int nj = 0;
+  for (int p = 0; p < npages; p++) {
+    JpegPage& jp = sl->jpg[(size_t)p];
+    if (!jp.on) continue;
+    if (!UPH_HIP(hipMemcpyAsync(djpg + off, jp.host.as(), jp.bytes, hipMemcpyHostToDevice, st)))
+      return false;
+    if (jp.dev) {
+      const JdecHeader& hd = *jp.host.as<const JdecHeader>();
+      hjob[nj++] = JdecJob{djpg + off, sl->djpk.as() + poff, sl->djsc.as() + soff, sl->djst.as<int32_t>() + p};
+      poff += up256((size_t)jp.h.total_bytes);
+      soff += up256(jdec_scratch_bytes(hd));
+    }
+    off += up256(jp.bytes);
+  }
+  if (nj) {
+    if (!UPH_HIP(hipMemcpyAsync(sl->djob.as(), hjob, sizeof(JdecJob) * (size_t)nj, hipMemcpyHostToDevice, st)) ||
+        !jdec_launch_batch(sl->djob.as<JdecJob>(), nj, max_nsub, max_nmac, st))
+      return false;
+  }
+  // JPEG 2000 pages: every code-block of the chunk in one launch (offsets
+  // made chunk-wide), into one coefficient buffer
+  {
+    int64_t nj = 0, coefs = 0;
+    int maxw = 0, maxh = 0;
+    for (int p = 0; p < npages; p++) {
+      const JpegPage& jp = sl->jpg[(size_t)p];
+      if (!jp.on || !jp.j2k) continue;
+      nj += jp.njobs;
+      coefs += jp.img.coef_elems;
+      maxw = std::max(maxw, jp.maxw);
+      maxh = std::max(maxh, jp.maxh);
+    }
+    if (coefs > 0) {
+      const int nslots = (int)std::min<int64_t>((nj + 63) / 64, 1024);
+      if (!grow(sl->dj2c, (size_t)coefs * 4) ||
+          !grow(sl->dj2t, (size_t)std::max(nslots, 1) * j2k::t1_slot_bytes(maxw, maxh)) ||
+          !grow(sl->dj2j, sizeof(j2k::T1Job) * (size_t)std::max<int64_t>(nj, 1)) ||
+          !sl->hj2j.reserve(sizeof(j2k::T1Job) * (size_t)nj + 256))
+        return false;
+      j2k::T1Job* const hj2j = sl->hj2j.as<j2k::T1Job>();
+      size_t o = 0;
+      int64_t q = 0, cb = 0;
+      for (int p = 0; p < npages; p++) {
+        const JpegPage& jp = sl->jpg[(size_t)p];
+        if (!jp.on) continue;
+        if (jp.j2k) {
+          const j2k::T1Job* pj = jp.host.as<const j2k::T1Job>();
+          for (int i = 0; i < jp.njobs; i++) {
+            j2k::T1Job t = pj[i];
+            t.data += (uint32_t)(o + jp.jobs_bytes);
+            t.out += cb;
+            hj2j[q++] = t;
+          }
+          cb += jp.img.coef_elems;
+        }
+        o += up256(jp.bytes);
+      }
+      if (o > 0xFFFFFFF0u) return fail("jp2: chunk too large for 32-bit codeword offsets");
+      if (!UPH_HIP(hipMemcpyAsync(sl->dj2j.as(), hj2j, sizeof(j2k::T1Job) * (size_t)nj,
+                                  hipMemcpyHostToDevice, st)) ||
+          !UPH_HIP(hipMemsetAsync(sl->dj2c.as(), 0, (size_t)coefs * 4, st)) ||
+          !j2k::t1_launch(sl->dj2j.as<j2k::T1Job>(), (int)nj, djpg, sl->dj2c.as<uint32_t>(), sl->dj2t.as(), nslots,
+                          maxw, maxh, st))
+        return false;
+    }
+  }
+  // pixels: each page from its packed coefficients into its input slot
+  off = 0;
+  int k = 0;
+  int64_t cb = 0;
+  for (int p = 0; p < npages; p++) {
+    JpegPage& jp = sl->jpg[(size_t)p];
+    if (!jp.on) continue;
+    int64_t pitch = 0;
+    uint8_t* dst = (uint8_t*)uphip_batch_input_ptr(sl->b, p, &pitch);
+    if (jp.j2k) {
+      if (!dst || !j2k::decode_launch(jp.img, sl->dj2c.as<uint32_t>() + cb, dst, pitch, dscr, st)) return false;
+      cb += jp.img.coef_elems;
+      off += up256(jp.bytes);
+      continue;
+    }
+    const uint8_t* packed = jp.dev ? hjob[k++].packed : djpg + off;
+    if (!dst || !jpeg_launch(jp.h, packed, dscr, dst, pitch, st)) return false;
+    off += up256(jp.bytes);
+  }
+  return true;
+}
+
+// The chunk's output pages as lossless JPEG 2000 code-blocks, queued on the
+// batch's stream once its run has finished: per sub-batch of pages the
+// forward transforms of each page, one code-block launch, the packing into
+// one buffer (offsets chained across sub-batches); then the offsets, lengths
+// and plane counts to pinned memory.  The store tasks copy each page's
+// packed bytes and write its packets and file.
+bool jp2_chunk_submit(UphipRunner* r, Slot* sl, int npg) {
+  if (npg <= 0) return true;
+  std::vector<const uint8_t*> src((size_t)npg);
+  int64_t pitch = 0;
+  int32_t w = 0, h = 0, fmt = 0;
+  for (int i = 0; i < npg; i++) {
+    const void* p = nullptr;
+    if (uphip_batch_jpeg_page(sl->b, i, &p, &pitch, &w, &h, &fmt) != 0) return false;
+    src[(size_t)i] = (const uint8_t*)p;
+  }
+  if (fmt != UPHIP_FMT_GRAY8 && fmt != UPHIP_FMT_RGB24) return fail("sink_jp2: GRAY8 or RGB24 sheets only");
+  j2k::Image& img = sl->j2img;
+  std::vector<j2k::T1EncJob> page;
+  size_t obytes = 0;
+  if (!j2k::encode_geometry(w, h, fmt == UPHIP_FMT_GRAY8 ? 1 : 3, &img) ||
+      !j2k::encode_jobs(img, &page, &obytes))
+    return false;
+  const int J = (int)page.size();
+  sl->j2jobs = J;
+  int maxw = 1, maxh = 1;
+  for (const j2k::T1EncJob& j : page) {
+    maxw = std::max(maxw, (int)j.w);
+    maxh = std::max(maxh, (int)j.h);
+  }
+  const int P = std::min(npg, kJ2kSubBatch);
+  const int nslots = std::min((P * J + 63) / 64, 1024);
+  const size_t cb = up256((size_t)P * img.coef_elems * 4), tb = up256((size_t)img.coef_elems * 4);
+  const size_t ob = up256((size_t)P * obytes), sb = up256((size_t)nslots * j2k::t1enc_slot_bytes(maxw, maxh));
+  const size_t jb = up256(sizeof(j2k::T1EncJob) * (size_t)P * J);
+  const size_t nj = (size_t)npg * J;
+  const size_t lb = up256(4 * nj), fb = up256(4 * (nj + 1)), nb = up256(nj), eb = 256;
+  // packed codewords: the pages' raw bytes and a half more (lossless files
+  // of 8-bit pages stay below their samples); a chunk past it fails loudly
+  const uint64_t pk = (uint64_t)npg * ((uint64_t)img.coef_elems * 3 / 2 + 65536);
+  const size_t need = cb + tb + ob + sb + jb + lb + fb + nb + eb + up256(pk);
+  const size_t hjobs = jb;
+  const size_t hneed = hjobs + 4 * (nj + 1) + 4 * nj + nj + 64;
+  if (!sl->dj2e.reserve(need) || !sl->hj2e.reserve(hneed)) return false;
+  uint8_t* a = sl->dj2e.as();
+  uint32_t* dcoef = (uint32_t*)a;
+  void* dtmp = a + cb;
+  uint8_t* dout = a + cb + tb;
+  void* dscr = a + cb + tb + ob;
+  j2k::T1EncJob* djobs = (j2k::T1EncJob*)(a + cb + tb + ob + sb);
+  uint32_t* dlen = (uint32_t*)(a + cb + tb + ob + sb + jb);
+  uint32_t* doff = (uint32_t*)(a + cb + tb + ob + sb + jb + lb);
+  uint8_t* dnb = a + cb + tb + ob + sb + jb + lb + fb;
+  int32_t* derr = (int32_t*)(a + cb + tb + ob + sb + jb + lb + fb + nb);
+  uint8_t* dpk = a + cb + tb + ob + sb + jb + lb + fb + nb + eb;
+  sl->dj2pk = dpk;
+  hipStream_t st = (hipStream_t)uphip_batch_stream(sl->b);
+  // the jobs of a sub-batch: page p's blocks with its coefficient and output
+  // offsets (the same for every sub-batch: staged once)
+  j2k::T1EncJob* sub = sl->hj2e.as<j2k::T1EncJob>();  // pinned: the copy is asynchronous
+  for (int p = 0; p < P; p++)
+    for (int i = 0; i < J; i++) {
+      j2k::T1EncJob t = page[(size_t)i];
+      t.in += (int64_t)p * img.coef_elems;
+      t.out += (uint32_t)((size_t)p * obytes);
+      sub[(size_t)p * J + i] = t;
+    }
+  if (!UPH_HIP(hipMemcpyAsync(djobs, sub, sizeof(j2k::T1EncJob) * (size_t)P * J, hipMemcpyHostToDevice, st)) ||
+      !UPH_HIP(hipMemsetAsync(doff, 0, 4, st)) || !UPH_HIP(hipMemsetAsync(derr, 0, 4, st)))
+    return false;
+  for (int p0 = 0; p0 < npg; p0 += P) {
+    const int n = std::min(P, npg - p0);
+    for (int p = 0; p < n; p++)
+      if (!j2k::encode_launch(img, src[(size_t)(p0 + p)], pitch, dcoef + (size_t)p * img.coef_elems, dtmp, st))
+        return false;
+    const size_t j0 = (size_t)p0 * J;
+    if (!j2k::t1enc_launch(djobs, n * J, dcoef, dout, dlen + j0, dnb + j0, dscr, nslots, maxw, maxh, st) ||
+        !j2k::t1enc_pack(djobs, n * J, dout, dlen + j0, doff + j0, dpk, pk, derr, true, st))
+      return false;
+  }
+  sl->hj2off = (uint32_t*)(sl->hj2e.as() + hjobs);
+  sl->hj2len = sl->hj2off + nj + 1;
+  sl->hj2nb = (uint8_t*)(sl->hj2len + nj);
+  sl->hj2err = (int32_t*)(((uintptr_t)(sl->hj2nb + nj) + 3) & ~(uintptr_t)3);
+  return UPH_HIP(hipMemcpyAsync(sl->hj2off, doff, 4 * (nj + 1), hipMemcpyDeviceToHost, st)) &&
+         UPH_HIP(hipMemcpyAsync(sl->hj2len, dlen, 4 * nj, hipMemcpyDeviceToHost, st)) &&
+         UPH_HIP(hipMemcpyAsync(sl->hj2nb, dnb, nj, hipMemcpyDeviceToHost, st)) &&
+         UPH_HIP(hipMemcpyAsync(sl->hj2err, derr, 4, hipMemcpyDeviceToHost, st));
+}
+
+}  // namespace uph
