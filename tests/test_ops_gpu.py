@@ -95,6 +95,33 @@ def test_resize_and_replace(hip, oracle, fmt, size):
     assert_same(d.to_host(), ho)
 
 
+FIT_TARGETS = [(100, 100), (60, 90)]   # the truncating fit; fit by width, padded vertically
+
+
+@pytest.mark.parametrize("fmt", [A.FMT_GRAY8, A.FMT_RGB24, A.FMT_MONOWHITE])
+@pytest.mark.parametrize("interp", [A.INTERP_NN, A.INTERP_LINEAR])
+@pytest.mark.parametrize("size", FIT_TARGETS)
+def test_resize_and_replace_fit(hip, oracle, fmt, interp, size):
+    h = make_image(120, 90, fmt, seed=8)
+    d = hip.upload(h)
+    hip.resize_and_replace(d, A.RectangleSize(*size), interp)
+    ho = oracle.resize_and_replace(h, A.RectangleSize(*size), interp)
+    assert (ho.width, ho.height) == size
+    assert_same(d.to_host(), ho)
+
+
+@pytest.mark.parametrize("sfmt", [A.FMT_GRAY8, A.FMT_RGB24, A.FMT_MONOWHITE])
+@pytest.mark.parametrize("tsize", FIT_TARGETS)
+def test_center_image_fit(hip, oracle, sfmt, tsize):
+    # a 120 x 90 source into each target: cropped in x, padded (or exact) in y
+    s = make_image(120, 90, sfmt, seed=5)
+    t = make_image(130, 110, A.FMT_RGB24, seed=6, background=(0, 0, 0))
+    ds, dt = hip.upload(s), hip.upload(t)
+    hip.center_image(ds, dt, A.Point(7, 3), A.RectangleSize(*tsize))
+    oracle.center_image(s, t, A.Point(7, 3), A.RectangleSize(*tsize))
+    assert_same(dt.to_host(), t)
+
+
 @pytest.mark.parametrize("fmt", FORMATS)
 @pytest.mark.parametrize("direction", [1, -1])
 @pytest.mark.parametrize("size", [(97, 61), (16, 9), (1, 5)])

@@ -44,11 +44,15 @@ def check(oracle, opts, sheets, what=""):
     for s, pages in enumerate(sheets):
         exp, erep = oracle_sheet(oracle, opts, pages)
         assert_same(outs[s], exp, "%s sheet %d" % (what, s))
-        assert reps[s].mask_count == erep.mask_count
-        for i in range(min(erep.mask_count, A.MAX_PAGES)):
-            assert np.float32(reps[s].rotation[i]).tobytes() == \
-                np.float32(erep.rotation[i]).tobytes(), "rotation %d" % i
+        assert_report(reps[s], erep)
     return outs
+
+
+def assert_report(rep, erep):
+    assert rep.mask_count == erep.mask_count
+    for i in range(min(erep.mask_count, A.MAX_PAGES)):
+        assert np.float32(rep.rotation[i]).tobytes() == \
+            np.float32(erep.rotation[i]).tobytes(), "rotation %d" % i
 
 
 def synth(w, h, page, fmt=A.FMT_GRAY8, threshold=170):
@@ -341,7 +345,7 @@ def test_fused_and_unfused_decode_agree(hip, oracle):
     # match plane and the noise- and blurfilter their bit-planes) and B with
     # tightly packed rows, which the plain copy decode takes and every filter
     # computes its own inputs.  The ABI cannot report which decode ran: the
-    # test relies on decode_fused's alignment condition (pipeline.hip,
+    # test relies on decode_fused's alignment condition (pipeline_run.hip,
     # `((uintptr_t)src & 15) || (spitch & 15) || (sstride & 15)` -> not fused),
     # which B's pitch fails and A's buffer meets.
     opts = oracle.default_options()
@@ -371,6 +375,81 @@ def test_fused_and_unfused_decode_agree(hip, oracle):
         assert_same(unfused[s], fused[s], "unfused vs fused sheet %d" % s)
         exp, _ = oracle_sheet(oracle, opts, [pages[s]])
         assert_same(fused[s], exp, "fused sheet %d" % s)
+
+
+@pytest.mark.parametrize("order", [(0, 1, 0), (1, 0, 1)])
+def test_one_batch_both_decodes(hip, oracle, order):
+    # One batch fed two device buffers in turn, as in
+    # test_fused_and_unfused_decode_agree: rows 640 bytes apart (the fused
+    # decode) and tightly packed at 620 (the copy decode).
+    # Each run finds its own argument blocks whatever the run before it was.
+    opts = oracle.default_options()
+    w, h = SMALL
+    pages = [speckled(w, h, p, k, 10 * p + k) for p, k in ((3, 40), (5, 110))]
+    n = len(pages)
+    pitches = (640, w)
+    assert pitches[0] % 16 == 0 and pitches[1] % 16 != 0
+    exp =[oracle_sheet(oracle, opts, [p]) for p in pages]
+    bufs = []
+    b = Batch(opts, n, w, h, A.FMT_GRAY8)
+    try:
+        for pitch in pitches:
+            host = np.zeros((n, h, pitch), np.uint8)
+            for s, p in enumerate(pages):
+                host[s, :, :w] = p.payload()
+            buf = DeviceBuffer(host.nbytes)
+            bufs.append(buf)
+            assert buf.ptr % 16 == 0
+            assert buf.lib.uphip_memcpy_htod(buf.ptr, host.ctypes.data, host.nbytes) == 0
+        for run, k in enumerate(order):
+            b.run_device(n, bufs[k].ptr, pitches[k], pitches[k] * h)
+            b.wait()
+            for s in range(n):
+                assert_same(b.output(s), exp[s][0], "run %d (pitch %d) sheet %d" % (run, pitches[k], s))
+                assert_report(b.report(s), exp[s][1])
+    finally:
+        b.close()
+        for buf in bufs:
+            buf.close()
+
+
+# The size chains (stretch, zoom, page size, rotate) on a 120 x 90 page with
+# nothing else on: options and the size the oracle gives the sheet.
+SIZE_CHAINS = {
+    "stretch": (dict(stretch_size=(150, 100)), (150, 100)),
+    "page_by_width": (dict(page_size=(60, 90)), (60, 90)),       # padded vertically
+    "page_by_height": (dict(page_size=(120, 45)), (120, 45)),    # padded horizontally
+    "page_equal_ratios": (dict(page_size=(240, 180)), (240, 180)),  # no pad
+    "page_truncating": (dict(page_size=(100, 100)), (100, 100)),
+    "stretch_page": (dict(stretch_size=(150, 100), page_size=(100, 100)), (100, 100)),
+    "zoom_page": (dict(pre_zoom_factor=0.5, page_size=(70, 40)), (70, 40)),
+    "sheet_size": (dict(sheet_size=(100, 100)), (100, 100)),     # decode crops in x, pads in y
+    "post": (dict(post_rotate=90, post_stretch_size=(80, 100), post_zoom_factor=2,
+                  post_page_size=(150, 230)), (150, 230)),
+}
+SIZE_CHAIN_CASES = [(name, interp) for name in SIZE_CHAINS
+                    for interp in ((A.INTERP_NN, A.INTERP_LINEAR) if name.startswith("page_") else (None,))]
+
+
+@pytest.mark.parametrize("name,interp", SIZE_CHAIN_CASES)
+def test_size_chain(hip, oracle, name, interp):
+    fields, size = SIZE_CHAINS[name]
+    opts = oracle.default_options()
+    opts.disable = A.NO_PROCESSING
+    if interp is not None:
+        opts.interpolate_type = interp
+    for k, v in fields.items():
+        setattr(opts, k, A.RectangleSize(*v) if isinstance(v, tuple) else v)
+    sheets = [[synth(120, 90, 1)], [synth(120, 90, 4)]]
+    outs = check(oracle, opts, sheets, name)
+    exp, _ = oracle_sheet(oracle, opts, sheets[0])
+    assert (exp.width, exp.height) == size
+    b = Batch(opts, 2, 120, 90, A.FMT_GRAY8)
+    try:
+        assert (b.out_width, b.out_height) == (exp.width, exp.height)
+    finally:
+        b.close()
+    assert (outs[0].width, outs[0].height) == size
 
 
 def test_noisefilter_sequential_intensity(hip, oracle):
@@ -617,7 +696,7 @@ def _blank_band(w, h, page, top, bottom):
 @pytest.mark.parametrize("align", ["center", "top", "bottom_right"])
 def test_chained_center_border_align(hip, oracle, margins, align):
     """The centring move, the border scan and the masked align move chained
-    (pipeline.hip chain_center_align, kernels_move.hip k_move_chain_g16):
+    (pipeline_plan.hip chain_center_align, kernels_move.hip k_move_chain_g16):
     the scan first counts only the rows within 320 of each edge; pages whose
     margin is wider (the top, the bottom or both blanked past 320 rows) make
     it count the middle rows and scan again.  Whole sheets against the

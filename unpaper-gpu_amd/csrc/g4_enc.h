@@ -24,6 +24,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "buffer.h"
+
 namespace uph {
 
 // The pages of one encode, all of one size: page p lies in sheet
@@ -57,14 +59,12 @@ bool g4_emit(const G4Pages& pg, const G4Launch& l, const int64_t* rowoff, const 
 // grown on demand (the stream is waited for only then).
 struct G4Context {
   int device = -1;
-  int64_t* rowoff = nullptr;
-  int64_t* meta = nullptr;  // sizes[n] then offsets[n]
-  uint8_t* out = nullptr;
-  size_t rowoff_cap = 0, meta_cap = 0, out_cap = 0;  // bytes
-  int64_t* host_sizes = nullptr;  // pinned: sizes[n] of the last encode
-  int sizes_cap = 0;
+  Buffer rowoff{Buffer::Device};
+  Buffer meta{Buffer::Device};        // int64: sizes[n] then offsets[n]
+  Buffer out{Buffer::Device};         // the packed streams
+  Buffer host_sizes{Buffer::Pinned};  // int64: sizes[n] of the last encode
   int n = 0;
-  ~G4Context();
+  ~G4Context();  // selects the device; the buffers release after it
   // zeroes the output, queues the encode of pg (pages above `share` bytes are
   // left out and sized -1) and the copy of the sizes into host_sizes
   bool encode_async(const G4Pages& pg, int64_t share, hipStream_t st);

@@ -266,21 +266,7 @@ void jenc_carve(const JencGeom& g, int n, uint8_t* meta, JencBuffers* b) {
 // JencContext: the device buffers of one encoder (a batch's, or a thread's
 // for uphip_jpeg_encode), grown on demand and reused.
 // ---------------------------------------------------------------------------
-JencContext::~JencContext() { release(); }
-
-void JencContext::release() {
-  if (device >= 0) hipSetDevice(device);
-  for (void* p : {(void*)tables, (void*)header, (void*)meta, (void*)bits, (void*)out})
-    if (p) hipFree(p);
-  if (host_sizes) hipHostFree(host_sizes);
-  tables = nullptr;
-  header = meta = out = nullptr;
-  bits = nullptr;
-  host_sizes = nullptr;
-  meta_cap = bits_cap = out_cap = 0;
-  sizes_cap = 0;
-  quality = -1;
-}
+JencContext::~JencContext() { if (device >= 0) hipSetDevice(device); }
 
 bool JencContext::setup(int32_t w, int32_t h, int32_t fmt, int32_t sampling, int32_t q, int nimg,
                         int64_t cap_words, int64_t out_bytes, hipStream_t st) {
@@ -290,38 +276,18 @@ bool JencContext::setup(int32_t w, int32_t h, int32_t fmt, int32_t sampling, int
   device = current_device();
   const size_t meta_need = jenc_meta_bytes(ng, nimg);
   const size_t bits_need = (size_t)cap_words * 4 * nimg;
-  const bool grow = meta_need > meta_cap || bits_need > bits_cap || (size_t)out_bytes > out_cap ||
-                    nimg > sizes_cap || !tables;
+  const size_t sizes_need = 16 * (size_t)nimg;
+  const bool grow = meta_need > meta.capacity() || bits_need > bits.capacity() ||
+                    (size_t)out_bytes > out.capacity() || sizes_need > host_sizes.capacity() ||
+                    !tables.capacity();
   const bool retab = q != quality || ng.w != g.w || ng.h != g.h || ng.mode != g.mode;
   if (grow || retab) {
     // the stream's earlier encodes are the only readers of the old buffers
     if (!UPH_HIP(hipStreamSynchronize(st))) return false;
   }
-  auto regrow = [](auto** p, size_t* cap, size_t need) -> bool {
-    if (need <= *cap && *p) return true;
-    if (*p) hipFree(*p);
-    *p = nullptr;
-    *cap = 0;
-    if (!UPH_HIP(hipMalloc((void**)p, std::max<size_t>(need, 256)))) return false;
-    *cap = std::max<size_t>(need, 256);
-    return true;
-  };
-  if (!regrow(&meta, &meta_cap, meta_need) || !regrow(&bits, &bits_cap, bits_need) ||
-      !regrow(&out, &out_cap, (size_t)out_bytes))
+  if (!meta.reserve(meta_need) || !bits.reserve(bits_need) || !out.reserve((size_t)out_bytes) ||
+      !tables.reserve(sizeof(JencTables)) || !header.reserve(1024) || !host_sizes.reserve(sizes_need))
     return false;
-  if (!tables) {
-    if (!UPH_HIP(hipMalloc((void**)&tables, sizeof(JencTables))) ||
-        !UPH_HIP(hipMalloc((void**)&header, 1024)))
-      return false;
-  }
-  if (nimg > sizes_cap) {
-    if (host_sizes) hipHostFree(host_sizes);
-    host_sizes = nullptr;
-    sizes_cap = 0;
-    if (!UPH_HIP(hipHostMalloc((void**)&host_sizes, 16 * (size_t)nimg, hipHostMallocDefault)))
-      return false;
-    sizes_cap = nimg;
-  }
   if (retab) {
     JencTables ht;
     jenc_tables(q, &ht);
@@ -329,8 +295,8 @@ bool JencContext::setup(int32_t w, int32_t h, int32_t fmt, int32_t sampling, int
     const int hb = jenc_header(ng, q, hdr, (int)sizeof(hdr));
     if (hb > (int)sizeof(hdr)) return fail("jpeg encode: header too long");
     ng.header_bytes = hb;
-    if (!UPH_HIP(hipMemcpy(tables, &ht, sizeof(ht), hipMemcpyHostToDevice)) ||
-        !UPH_HIP(hipMemcpy(header, hdr, (size_t)hb, hipMemcpyHostToDevice)))
+    if (!UPH_HIP(hipMemcpy(tables.as(), &ht, sizeof(ht), hipMemcpyHostToDevice)) ||
+        !UPH_HIP(hipMemcpy(header.as(), hdr, (size_t)hb, hipMemcpyHostToDevice)))
       return false;
     quality = q;
   } else {
@@ -341,17 +307,17 @@ bool JencContext::setup(int32_t w, int32_t h, int32_t fmt, int32_t sampling, int
   g = ng;
   n = nimg;
   B = JencBuffers{};
-  jenc_carve(g, n, meta, &B);
-  B.bits = bits;
-  B.out = out;
-  B.header = header;
-  B.tables = tables;
+  jenc_carve(g, n, meta.as(), &B);
+  B.bits = bits.as<uint32_t>();
+  B.out = out.as();
+  B.header = header.as();
+  B.tables = tables.as<JencTables>();
   return true;
 }
 
 bool JencContext::encode_async(hipStream_t st) {
   return jenc_launch(g, B, n, st) &&
-         UPH_HIP(hipMemcpyAsync(host_sizes, B.sizes, 16 * (size_t)n, hipMemcpyDeviceToHost, st));
+         UPH_HIP(hipMemcpyAsync(host_sizes.as(), B.sizes, 16 * (size_t)n, hipMemcpyDeviceToHost, st));
 }
 
 }  // namespace uph
@@ -385,7 +351,8 @@ int64_t uphip_jpeg_encode(const void* device_src, int64_t pitch, int32_t width, 
     if (!UPH_HIP(hipMemcpyAsync(c.B.images, &im, sizeof(im), hipMemcpyHostToDevice, st)) ||
         !c.encode_async(st) || !UPH_HIP(hipStreamSynchronize(st)))
       return -1;
-    const int64_t size = c.host_sizes[0];
+    const int64_t* hs = c.host_sizes.as<int64_t>();
+    const int64_t size = hs[0];
     if (size == -1) {  // bit stream larger than guessed: its exact length
       uint64_t total = 0;
       if (!UPH_HIP(hipMemcpy(&total, c.B.tile_off + c.g.tiles, 8, hipMemcpyDeviceToHost))) return -1;
@@ -394,7 +361,7 @@ int64_t uphip_jpeg_encode(const void* device_src, int64_t pitch, int32_t width, 
     }
     if (size < 0) return fail("jpeg_encode: output buffer overflow"), -1;
     if (out && capacity >= size &&
-        !UPH_HIP(hipMemcpy(out, c.out + c.host_sizes[1], (size_t)size, hipMemcpyDeviceToHost)))
+        !UPH_HIP(hipMemcpy(out, c.B.out + hs[1], (size_t)size, hipMemcpyDeviceToHost)))
       return -1;
     return size;
   }

@@ -38,6 +38,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "buffer.h"
 #include "unpaper_hip.h"
 
 namespace uph {
@@ -99,17 +100,14 @@ struct JencContext {
   int device = -1;
   JencGeom g{};
   int quality = -1, n = 0;
-  JencTables* tables = nullptr;
-  uint8_t* header = nullptr;
-  uint8_t* meta = nullptr;
-  uint32_t* bits = nullptr;
-  uint8_t* out = nullptr;
-  size_t meta_cap = 0, bits_cap = 0, out_cap = 0;
-  int64_t* host_sizes = nullptr;  // pinned: sizes[n] then offsets[n] of the last encode
-  int sizes_cap = 0;
+  Buffer tables{Buffer::Device};      // one JencTables
+  Buffer header{Buffer::Device};      // the file header, up to 1024 bytes
+  Buffer meta{Buffer::Device};        // the per-tile arrays (jenc_carve)
+  Buffer bits{Buffer::Device};        // the bit streams
+  Buffer out{Buffer::Device};         // the packed files
+  Buffer host_sizes{Buffer::Pinned};  // int64: sizes[n] then offsets[n] of the last encode
   JencBuffers B{};
-  ~JencContext();
-  void release();
+  ~JencContext();  // selects the device; the buffers release after it
   // geometry, tables and buffers for nimg images; B.images is left to the caller
   bool setup(int32_t w, int32_t h, int32_t fmt, int32_t sampling, int32_t quality, int nimg,
              int64_t cap_words, int64_t out_bytes, hipStream_t st);

@@ -166,18 +166,6 @@ __global__ void k_g4_offsets(const int64_t* sizes, int64_t* offs, int n) {
   }
 }
 
-template <class T>
-bool regrow(T** p, size_t* cap, size_t need) {
-  need = std::max<size_t>(need, 256);
-  if (*p && need <= *cap) return true;
-  if (*p) hipFree(*p);
-  *p = nullptr;
-  *cap = 0;
-  if (!UPH_HIP(hipMalloc((void**)p, need))) return false;
-  *cap = need;
-  return true;
-}
-
 bool pages_ok(const G4Pages& pg, const char* who) {
   if (!pg.base) return fail("%s: null source", who);
   if (pg.width <= 0 || pg.width > (1 << 20) || pg.height <= 0 || pg.height > (1 << 20))
@@ -230,13 +218,7 @@ bool g4_emit(const G4Pages& pg, const G4Launch& l, const int64_t* rowoff, const 
   return UPH_HIP(hipGetLastError());
 }
 
-G4Context::~G4Context() {
-  if (device >= 0) hipSetDevice(device);
-  if (rowoff) hipFree(rowoff);
-  if (meta) hipFree(meta);
-  if (out) hipFree(out);
-  if (host_sizes) hipHostFree(host_sizes);
-}
+G4Context::~G4Context() { if (device >= 0) hipSetDevice(device); }
 
 bool G4Context::encode_async(const G4Pages& pg, int64_t share, hipStream_t st) {
   G4Launch l;
@@ -245,28 +227,22 @@ bool G4Context::encode_async(const G4Pages& pg, int64_t share, hipStream_t st) {
   const size_t rows_need = (size_t)pg.npages * pg.height * sizeof(int64_t);
   const size_t meta_need = (size_t)pg.npages * 2 * sizeof(int64_t);
   const size_t out_need = ((size_t)share * pg.npages + 3) / 4 * 4 + 4;
-  if (rows_need > rowoff_cap || meta_need > meta_cap || out_need > out_cap || pg.npages > sizes_cap) {
+  const size_t sizes_need = (size_t)pg.npages * sizeof(int64_t);
+  if (rows_need > rowoff.capacity() || meta_need > meta.capacity() || out_need > out.capacity() ||
+      sizes_need > host_sizes.capacity()) {
     // the stream's earlier encodes are the only users of the old buffers
     if (!UPH_HIP(hipStreamSynchronize(st))) return false;
-    if (!regrow(&rowoff, &rowoff_cap, rows_need) || !regrow(&meta, &meta_cap, meta_need) ||
-        !regrow(&out, &out_cap, out_need))
+    if (!rowoff.reserve(rows_need) || !meta.reserve(meta_need) || !out.reserve(out_need) ||
+        !host_sizes.reserve(sizes_need))
       return false;
-    if (pg.npages > sizes_cap) {
-      if (host_sizes) hipHostFree(host_sizes);
-      host_sizes = nullptr;
-      sizes_cap = 0;
-      if (!UPH_HIP(hipHostMalloc((void**)&host_sizes, sizeof(int64_t) * (size_t)pg.npages, hipHostMallocDefault)))
-        return false;
-      sizes_cap = pg.npages;
-    }
   }
   n = pg.npages;
-  int64_t* sizes = meta;
-  int64_t* offs = meta + pg.npages;
-  return UPH_HIP(hipMemsetAsync(out, 0, out_need, st)) &&
-         g4_measure(pg, l, rowoff, sizes, offs, share, st) && g4_emit(pg, l, rowoff, sizes, offs, out, st) &&
-         UPH_HIP(hipMemcpyAsync(host_sizes, sizes, sizeof(int64_t) * (size_t)pg.npages, hipMemcpyDeviceToHost,
-                                st));
+  int64_t* sizes = meta.as<int64_t>();
+  int64_t* offs = sizes + pg.npages;
+  return UPH_HIP(hipMemsetAsync(out.as(), 0, out_need, st)) &&
+         g4_measure(pg, l, rowoff.as<int64_t>(), sizes, offs, share, st) &&
+         g4_emit(pg, l, rowoff.as<int64_t>(), sizes, offs, out.as(), st) &&
+         UPH_HIP(hipMemcpyAsync(host_sizes.as(), sizes, sizes_need, hipMemcpyDeviceToHost, st));
 }
 
 }  // namespace uph
@@ -281,11 +257,11 @@ extern "C" int64_t uphip_g4_encode(const void* device_src, int64_t pitch, int32_
   if (!pages_ok(pg, "g4_encode") || !g4_plan(width, &l)) return -1;
   hipStream_t st = current_stream();
   // count, read the size, then emit into a buffer of exactly that size
-  int64_t* rowoff = nullptr;
-  uint8_t* stream = nullptr;
+  Buffer rows(Buffer::Device), stream(Buffer::Device);
   int64_t size = -1;
-  bool ok = UPH_HIP(hipMalloc((void**)&rowoff, sizeof(int64_t) * ((size_t)height + 2)));
+  bool ok = rows.reserve(sizeof(int64_t) * ((size_t)height + 2));
   if (ok) {
+    int64_t* rowoff = rows.as<int64_t>();
     int64_t* sizes = rowoff + height;
     int64_t* offs = sizes + 1;
     ok = g4_measure(pg, l, rowoff, sizes, offs, INT64_MAX, st) &&
@@ -294,13 +270,11 @@ extern "C" int64_t uphip_g4_encode(const void* device_src, int64_t pitch, int32_
     if (ok && size <= 0) ok = fail("g4_encode: the count pass gave no size");
     if (ok && out && capacity >= size) {
       const size_t padded = ((size_t)size + 3) / 4 * 4;  // the last word is written whole
-      ok = UPH_HIP(hipMalloc((void**)&stream, padded)) && UPH_HIP(hipMemsetAsync(stream, 0, padded, st)) &&
-           g4_emit(pg, l, rowoff, sizes, offs, stream, st) &&
-           UPH_HIP(hipMemcpyAsync(out, stream, (size_t)size, hipMemcpyDeviceToHost, st));
+      ok = stream.reserve(padded) && UPH_HIP(hipMemsetAsync(stream.as(), 0, padded, st)) &&
+           g4_emit(pg, l, rowoff, sizes, offs, stream.as(), st) &&
+           UPH_HIP(hipMemcpyAsync(out, stream.as(), (size_t)size, hipMemcpyDeviceToHost, st));
       ok = UPH_HIP(hipStreamSynchronize(st)) && ok;
     }
   }
-  if (stream) hipFree(stream);
-  if (rowoff) hipFree(rowoff);
   return ok ? size : -1;
 }

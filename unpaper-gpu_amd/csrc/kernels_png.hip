@@ -334,18 +334,6 @@ __global__ __launch_bounds__(kThreads) void k_png_stored(Shape s, const uint8_t*
   }
 }
 
-template <class T>
-bool regrow(T** p, size_t* cap, size_t need) {
-  need = std::max<size_t>(need, 256);
-  if (*p && need <= *cap) return true;
-  if (*p) hipFree(*p);
-  *p = nullptr;
-  *cap = 0;
-  if (!UPH_HIP(hipMalloc((void**)p, need))) return false;
-  *cap = need;
-  return true;
-}
-
 bool pages_ok(const PngPages& pg, Shape* s, const char* who) {
   if (!pg.plane[0]) return fail("%s: null source", who);
   if (pg.width <= 0 || pg.width > (1 << 20) || pg.height <= 0 || pg.height > (1 << 20))
@@ -378,16 +366,7 @@ bool png_plan(const Shape& s, PngLaunch* l) {
   return true;
 }
 
-PngContext::~PngContext() {
-  if (device >= 0) hipSetDevice(device);
-  if (filt) hipFree(filt);
-  if (segoff) hipFree(segoff);
-  if (segadler) hipFree(segadler);
-  if (tabs) hipFree(tabs);
-  if (meta) hipFree(meta);
-  if (out) hipFree(out);
-  if (host_sizes) hipHostFree(host_sizes);
-}
+PngContext::~PngContext() { if (device >= 0) hipSetDevice(device); }
 
 bool PngContext::encode_async(const PngPages& pg, hipStream_t st) {
   Shape s;
@@ -403,25 +382,26 @@ bool PngContext::encode_async(const PngPages& pg, hipStream_t st) {
   const size_t tabs_need = np * sizeof(PageTab);
   const size_t meta_need = np * 2 * sizeof(int64_t);
   const size_t out_need = ((size_t)stored_size(s.total) * np + 3) / 4 * 4 + 4;
-  if (filt_need > filt_cap || segoff_need > segoff_cap || segadler_need > segadler_cap || tabs_need > tabs_cap ||
-      meta_need > meta_cap || out_need > out_cap || pg.npages > sizes_cap) {
+  const size_t sizes_need = np * sizeof(int64_t);
+  if (filt_need > filt.capacity() || segoff_need > segoff.capacity() || segadler_need > segadler.capacity() ||
+      tabs_need > tabs.capacity() || meta_need > meta.capacity() || out_need > out.capacity() ||
+      sizes_need > host_sizes.capacity()) {
     // the stream's earlier encodes are the only users of the old buffers
     if (!UPH_HIP(hipStreamSynchronize(st))) return false;
-    if (!regrow(&filt, &filt_cap, filt_need) || !regrow(&segoff, &segoff_cap, segoff_need) ||
-        !regrow(&segadler, &segadler_cap, segadler_need) || !regrow(&tabs, &tabs_cap, tabs_need) ||
-        !regrow(&meta, &meta_cap, meta_need) || !regrow(&out, &out_cap, out_need))
+    if (!filt.reserve(filt_need) || !segoff.reserve(segoff_need) || !segadler.reserve(segadler_need) ||
+        !tabs.reserve(tabs_need) || !meta.reserve(meta_need) || !out.reserve(out_need) ||
+        !host_sizes.reserve(sizes_need))
       return false;
-    if (pg.npages > sizes_cap) {
-      if (host_sizes) hipHostFree(host_sizes);
-      host_sizes = nullptr;
-      sizes_cap = 0;
-      if (!UPH_HIP(hipHostMalloc((void**)&host_sizes, sizeof(int64_t) * np, hipHostMallocDefault))) return false;
-      sizes_cap = pg.npages;
-    }
   }
   n = pg.npages;
-  int64_t* sizes = meta;
-  int64_t* offs = meta + pg.npages;
+  int64_t* sizes = meta.as<int64_t>();
+  int64_t* offs = sizes + pg.npages;
+  // the kernels' views of the buffers
+  uint8_t* filt = this->filt.as();
+  int64_t* segoff = this->segoff.as<int64_t>();
+  uint2* segadler = this->segadler.as<uint2>();
+  PageTab* tabs = this->tabs.as<PageTab>();
+  uint8_t* out = this->out.as();
   if (!UPH_HIP(hipMemsetAsync(out, 0, out_need, st)) || !UPH_HIP(hipMemsetAsync(tabs, 0, tabs_need, st))) return false;
   allow_dynamic_lds((const void*)k_png_filter, l.lds_bytes);
   const unsigned pages = (unsigned)pg.npages;
@@ -442,7 +422,7 @@ bool PngContext::encode_async(const PngPages& pg, hipStream_t st) {
   hipLaunchKernelGGL(k_png_stored, dim3(copy_blocks, pages), dim3(kThreads), 0, st, s, (const uint8_t*)filt,
                      filt_stride, (const PageTab*)tabs, (const int64_t*)offs, out);
   return UPH_HIP(hipGetLastError()) &&
-         UPH_HIP(hipMemcpyAsync(host_sizes, sizes, sizeof(int64_t) * np, hipMemcpyDeviceToHost, st));
+         UPH_HIP(hipMemcpyAsync(host_sizes.as(), sizes, sizes_need, hipMemcpyDeviceToHost, st));
 }
 
 }  // namespace uph
@@ -459,14 +439,14 @@ extern "C" int64_t uphip_png_encode(const void* device_src, int64_t pitch, int32
   const PngPages pg{{(const uint8_t*)device_src, nullptr}, nullptr, 0, 0, pitch, 1, width, offset,
                     format, width, height, 1};
   if (!c.encode_async(pg, st) || !UPH_HIP(hipStreamSynchronize(st))) return -1;
-  const int64_t len = c.host_sizes[0];
+  const int64_t len = c.host_sizes.as<int64_t>()[0];
   if (len <= 0) return fail("png_encode: the scan gave no size"), -1;
   const int64_t size = uphip_png_wrap("", len, width, height, format, dpi, nullptr, 0);
   if (!out || size < 0) return size;
   if (capacity < size)
     return fail("png_encode: the file needs %lld bytes, the buffer has %lld", (long long)size, (long long)capacity), -1;
   std::vector<uint8_t> z((size_t)len);
-  if (!UPH_HIP(hipMemcpyAsync(z.data(), c.out, (size_t)len, hipMemcpyDeviceToHost, st)) ||
+  if (!UPH_HIP(hipMemcpyAsync(z.data(), c.out.as(), (size_t)len, hipMemcpyDeviceToHost, st)) ||
       !UPH_HIP(hipStreamSynchronize(st)))
     return -1;
   return uphip_png_wrap(z.data(), len, width, height, format, dpi, out, capacity);

@@ -10,6 +10,7 @@
 #include "mono_proxy.h"
 #include "runtime.h"
 #include "scan.h"
+#include "sheet_sizes.h"
 
 namespace uph {
 
@@ -151,31 +152,17 @@ void uphip_center_image(UphipImage source, UphipImage target, UphipPoint to,
                         UphipRectangleSize ts) {
   // center_image_cpu, blit.c:175-202
   if (!ok_image(source, "center_image") || !ok_image(target, "center_image")) return;
-  UphipPoint so{0, 0};
-  UphipRectangleSize ss{source.frame->width, source.frame->height};
+  const UphipRectangleSize ss{source.frame->width, source.frame->height};
   if (ss.width < ts.width || ss.height < ts.height)
     uphip_wipe_rectangle(target, from_rect(rect_from_size(to.x, to.y, ts.width, ts.height)),
                          target.background);
-  if (ss.width <= ts.width) {
-    to.x += (ts.width - ss.width) / 2;
-  } else {
-    so.x += (ss.width - ts.width) / 2;
-    ss.width = ts.width;
-  }
-  if (ss.height <= ts.height) {
-    to.y += (ts.height - ss.height) / 2;
-  } else {
-    so.y += (ss.height - ts.height) / 2;
-    ss.height = ts.height;
-  }
-  uphip_copy_rectangle(source, target, from_rect(rect_from_size(so.x, so.y, ss.width, ss.height)),
-                       to);
+  const Placement p = center_in(ss.width, ss.height, to.x, to.y, ts.width, ts.height);
+  uphip_copy_rectangle(source, target, from_rect(rect_from_size(p.sx, p.sy, p.w, p.h)),
+                       UphipPoint{p.tx, p.ty});
 }
 
 static int compare_sizes(UphipRectangleSize a, UphipRectangleSize b) {
-  // primitives.c:70-80
-  if (a.height == b.height && a.width == b.width) return 0;
-  return imin(a.height, a.width) < imin(b.height, b.width) ? -1 : 1;
+  return compare_sizes(a.width, a.height, b.width, b.height);
 }
 
 void uphip_stretch_and_replace(UphipImage* pImage, UphipRectangleSize size,
@@ -197,18 +184,8 @@ void uphip_resize_and_replace(UphipImage* pImage, UphipRectangleSize size,
   if (!pImage || !ok_image(*pImage, "resize_and_replace")) return;
   UphipRectangleSize is{pImage->frame->width, pImage->frame->height};
   if (compare_sizes(is, size) == 0) return;
-  const float hr = (float)size.width / (float)is.width;
-  const float vr = (float)size.height / (float)is.height;
   UphipRectangleSize ss;
-  if (hr < vr) {
-    ss.width = size.width;
-    ss.height = (int32_t)(is.height * hr);
-  } else if (vr < hr) {
-    ss.width = (int32_t)(is.width * vr);
-    ss.height = size.height;
-  } else {
-    ss = size;
-  }
+  aspect_fit(is.width, is.height, size.width, size.height, &ss.width, &ss.height);
   uphip_stretch_and_replace(pImage, ss, interp);
   if (size.width == ss.width && size.height == ss.height) return;
   UphipImage resized = uphip_create_compatible_image(*pImage, size, true);

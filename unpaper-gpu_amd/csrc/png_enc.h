@@ -34,6 +34,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "buffer.h"
 #include "png_enc_core.h"
 
 namespace uph {
@@ -64,18 +65,19 @@ bool png_plan(const pngenc::Shape& s, PngLaunch* l);
 // on demand (the stream is waited for only then).
 struct PngContext {
   int device = -1;
-  uint8_t* filt = nullptr;        // npages * filt_stride filtered bytes
-  int64_t* segoff = nullptr;      // per segment: token bits, then their prefix sum
-  uint2* segadler = nullptr;      // per segment: Adler sums
-  pngenc::PageTab* tabs = nullptr;
-  int64_t* meta = nullptr;        // sizes[n] then offsets[n]
-  uint8_t* out = nullptr;         // the packed streams
-  size_t filt_cap = 0, segoff_cap = 0, segadler_cap = 0, tabs_cap = 0, meta_cap = 0, out_cap = 0;  // bytes
-  int64_t* host_sizes = nullptr;  // pinned: sizes[n] of the last encode
-  int sizes_cap = 0;
+  Buffer filt{Buffer::Device};        // npages * filt_stride filtered bytes
+  Buffer segoff{Buffer::Device};      // int64 per segment: token bits, then their prefix sum
+  Buffer segadler{Buffer::Device};    // uint2 per segment: Adler sums
+  Buffer tabs{Buffer::Device};        // a pngenc::PageTab per page
+  Buffer meta{Buffer::Device};        // int64: sizes[n] then offsets[n]
+  Buffer out{Buffer::Device};         // the packed streams
+  Buffer host_sizes{Buffer::Pinned};  // int64: sizes[n] of the last encode
   int n = 0;
-  ~PngContext();
-  size_t device_bytes() const { return filt_cap + segoff_cap + segadler_cap + tabs_cap + meta_cap + out_cap; }
+  ~PngContext();  // selects the device; the buffers release after it
+  size_t device_bytes() const {
+    return filt.capacity() + segoff.capacity() + segadler.capacity() + tabs.capacity() + meta.capacity() +
+           out.capacity();
+  }
   // zeroes the output, queues the encode of pg and the copy of the sizes
   // into host_sizes
   bool encode_async(const PngPages& pg, hipStream_t st);
