@@ -9,6 +9,9 @@
 #                      under ASan/UBSan (host code only, no GPU)
 #   make sanitize_png -> tests/c/_build/png_enc_main: the lossless PNG encoder's
 #                      host twin under ASan/UBSan, stand-alone (host code only)
+#   make sanitize_tiff -> tests/c/_build/tiff_main: the TIFF reader (container
+#                      and strip decoder, the device kernels' host twin) under
+#                      ASan/UBSan over the files of a directory, stand-alone
 #   make lib DIAG=1 -> the same library with the timing diagnostics of
 #                      csrc/common.h (UPHIP_DIAG_*) compiled in; tuning only,
 #                      built into its own object dir.  The default build has none.
@@ -64,7 +67,7 @@ LLVMCC     := /opt/rocm/lib/llvm/bin/clang
 SANFLAGS   := -fsanitize=address,undefined -fno-sanitize-recover=undefined \
               -fno-omit-frame-pointer -g -O1
 
-.PHONY: all lib oracle ctest sanitize sanitize_png libm_check jdec_emul j2k_emul clean
+.PHONY: all lib oracle ctest sanitize sanitize_png sanitize_tiff libm_check jdec_emul j2k_emul clean
 all: lib oracle ctest libm_check jdec_emul j2k_emul
 
 lib: $(LIB)
@@ -110,7 +113,7 @@ $(LIBM_CHECK): tests/c/libm_check.cpp $(CSRC)/libm_glibc.h
 # One compiler (ROCm clang) for every object so that one sanitizer runtime
 # serves the program; the HIP sources are compiled for the host only.
 $(SANITIZE): tests/c/sanitize_main.c oracle/oracle.c oracle/oracle.h $(CSRC)/pnm.cpp $(CSRC)/png.cpp \
-             $(CSRC)/jpeg.cpp $(CSRC)/j2k.cpp $(CSRC)/pdf.cpp $(CSRC)/jbig2.cpp $(CSRC)/ccitt.cpp tests/c/san_stubs.cpp $(CSRC)/runtime.hip $(HDRS)
+             $(CSRC)/jpeg.cpp $(CSRC)/j2k.cpp $(CSRC)/pdf.cpp $(CSRC)/jbig2.cpp $(CSRC)/ccitt.cpp $(CSRC)/tiff.cpp tests/c/san_stubs.cpp $(CSRC)/runtime.hip $(HDRS)
 	@mkdir -p tests/c/_build/san
 	$(LLVMCC) $(SANFLAGS) -std=gnu11 -ffp-contract=off -c oracle/oracle.c -o tests/c/_build/san/oracle.o
 	$(LLVMCC) $(SANFLAGS) -std=gnu11 -Iinclude -c tests/c/sanitize_main.c -o tests/c/_build/san/main.o
@@ -128,6 +131,8 @@ $(SANITIZE): tests/c/sanitize_main.c oracle/oracle.c oracle/oracle.h $(CSRC)/pnm
 	  -Iinclude -I$(CSRC) -c $(CSRC)/jbig2.cpp -o tests/c/_build/san/jbig2.o
 	$(HIPCC) --cuda-host-only -x hip $(SANFLAGS) -std=c++17 -Wno-unused-result -Wno-unused-value \
 	  -Iinclude -I$(CSRC) -c $(CSRC)/ccitt.cpp -o tests/c/_build/san/ccitt.o
+	$(HIPCC) --cuda-host-only -x hip $(SANFLAGS) -std=c++17 -Wno-unused-result -Wno-unused-value \
+	  -Iinclude -I$(CSRC) -c $(CSRC)/tiff.cpp -o tests/c/_build/san/tiff.o
 	$(HIPCC) --cuda-host-only -x hip $(SANFLAGS) -std=c++17 -Wno-unused-result -Wno-unused-value \
 	  -Iinclude -I$(CSRC) -c tests/c/san_stubs.cpp -o tests/c/_build/san/san_stubs.o
 	$(HIPCC) --cuda-host-only -x hip $(SANFLAGS) -std=c++17 -Wno-unused-result -Wno-unused-value \
@@ -163,6 +168,20 @@ $(PNG_ENC_MAIN): tests/c/png_enc_main.cpp $(CSRC)/png_enc.cpp $(CSRC)/png_enc_co
 
 sanitize_png: $(PNG_ENC_MAIN)
 	ASAN_OPTIONS=detect_leaks=1 UBSAN_OPTIONS=print_stacktrace=1 $(PNG_ENC_MAIN)
+
+# the TIFF reader with its own main and error reporting: every *.tif of the
+# directory TIFF_DIR probed and read page by page into guarded buffers; a file
+# may fail to decode, the program fails only when a sanitizer fires or a read
+# writes outside its page
+TIFF_MAIN := tests/c/_build/tiff_main
+TIFF_DIR  ?= tests/c/_build/tiff_cases
+$(TIFF_MAIN): tests/c/tiff_main.cpp $(CSRC)/tiff.cpp $(CSRC)/ccitt.cpp $(HDRS)
+	@mkdir -p tests/c/_build
+	$(HIPCC) --cuda-host-only -x hip $(SANFLAGS) -std=c++17 -Wall -Wno-unused-function -Wno-unused-result \
+	  -Wno-unused-value -Iinclude -I$(CSRC) tests/c/tiff_main.cpp $(CSRC)/tiff.cpp $(CSRC)/ccitt.cpp -o $@ -lz
+
+sanitize_tiff: $(TIFF_MAIN)
+	ASAN_OPTIONS=detect_leaks=1 UBSAN_OPTIONS=print_stacktrace=1 $(TIFF_MAIN) $(TIFF_DIR)
 
 clean:
 	rm -rf $(PKG)/build $(PKG)/build_diag $(PKG)/lib $(PKG)/lib_diag oracle/_build oracle/_ref tests/c/_build

@@ -658,7 +658,48 @@ int64_t uphip_png_encode(const void *device_src, int64_t pitch, int32_t offset, 
  * included.  Sizes and errors as uphip_png_encode.  No reference peer. */
 int64_t uphip_png_wrap(const void *stream, int64_t len, int32_t width, int32_t height,
                        int32_t format, int32_t dpi, void *out, int64_t capacity);
-/* Any codec, picked by the file's signature (PNG, JPEG, JPEG 2000 or PNM). */
+/* TIFF third of loadImage (file.c:29-131; the reference reads TIFF through
+ * FFmpeg), without libtiff.  Classic TIFF of either byte order, strips,
+ * PlanarConfiguration 1; 1-bit Photometric 0 -> MONOWHITE and 1 -> MONOBLACK
+ * (bits as stored), 8-bit gray -> GRAY8 (MinIsWhite inverted), gray + one
+ * extra sample -> Y400A, 8/8/8 -> RGB24, palette -> RGB24 (the PAL8 case,
+ * file.c:110-120); Compression 1, 32773 (PackBits), 5 (LZW), 8 / 32946
+ * (Deflate), 3 and 4 (Group 3 / 4); Predictor 2 and FillOrder 2; Orientation
+ * ignored.  BigTIFF, tiles, PlanarConfiguration 2, 2/4/16-bit samples, RGBA,
+ * YCbCr / CMYK / CIELab and other compressions fail with an error that names
+ * the tag and its value.
+ *   uphip_tiff_probe / _read:  the first image, decoded on the host.
+ *   uphip_tiff_open ...:       a document of one page per IFD; page_probe
+ *                              also gives the resolution (dpi_out[0..1], x and
+ *                              y, 0 when the file has none; may be NULL);
+ *                              page_on_device: 1 when the page qualifies for
+ *                              the runner's device route (PackBits or LZW,
+ *                              every strip at most 65536 decoded bytes, at
+ *                              least 8 strips), 0 when it is decoded on the
+ *                              load tasks whatever the flags, -1 on error.
+ *   uphip_tiff_decode:         page `page` of a file image in memory decoded
+ *                              on the current device into device memory (rows
+ *                              `pitch` apart; only the row's bytes are
+ *                              written): a lane per strip, then a wave per row
+ *                              (csrc/tiff_dec.h).  PackBits and LZW pages with
+ *                              strips of at most 65536 bytes, any number of
+ *                              them.  info: in = expected geometry when
+ *                              width > 0, out = geometry.  Synchronous; -1
+ *                              with the strip's error. */
+typedef struct UphipTiffDocument UphipTiffDocument;
+int uphip_tiff_probe(const char *path, UphipPnmInfo *info);
+int uphip_tiff_read(const char *path, void *dst, int64_t linesize,
+                    const UphipPnmInfo *expect);
+UphipTiffDocument *uphip_tiff_open(const char *path);
+void uphip_tiff_close(UphipTiffDocument *doc);
+int uphip_tiff_page_count(UphipTiffDocument *doc);
+int uphip_tiff_page_probe(UphipTiffDocument *doc, int page, UphipPnmInfo *info, float *dpi_out);
+int uphip_tiff_read_page(UphipTiffDocument *doc, int page, void *dst, int64_t linesize,
+                         const UphipPnmInfo *expect);
+int uphip_tiff_page_on_device(UphipTiffDocument *doc, int page);
+int uphip_tiff_decode(const void *data, size_t size, int32_t page, void *device_dst,
+                      int64_t pitch, UphipPnmInfo *info);
+/* Any codec, picked by the file's signature (PNG, JPEG, JPEG 2000, TIFF or PNM). */
 int uphip_image_probe(const char *path, UphipPnmInfo *info);
 int uphip_image_read(const char *path, void *dst, int64_t linesize,
                      const UphipPnmInfo *expect);
@@ -836,9 +877,20 @@ UphipSource *uphip_source_callback(UphipLoadFn load, void *user);
  * through the staged path. */
 UphipSource *uphip_source_memory(const void *base, int64_t linesize,
                                  int64_t page_stride, int64_t npages);
-/* page i decoded from paths[i] (PNM, PNG or JPEG, uphip_image_read) straight into
+/* page i decoded from paths[i] (PNM, PNG, JPEG or TIFF, uphip_image_read) straight into
  * the staging slot */
 UphipSource *uphip_source_pnm(const char *const *paths, int64_t npaths);
+/* A multi-page TIFF: input page i is IFD i of the file (uphip_tiff_open).
+ * By default every page is decoded on the load tasks (measured faster on an
+ * MI355X than the device route); UPHIP_TIFF_HOST_DECODE says the
+ * same explicitly.  With UPHIP_TIFF_DEVICE_DECODE the pages for which
+ * uphip_tiff_page_on_device gives 1 cross PCIe as compressed strips and are
+ * decoded on the slot's stream into the batch's input slot; a corrupt strip
+ * fails its job, the rest of the chunk goes on.  TIFFs named in a
+ * uphip_source_pnm list (their first image) take the default route. */
+#define UPHIP_TIFF_HOST_DECODE 1
+#define UPHIP_TIFF_DEVICE_DECODE 2
+UphipSource *uphip_source_tiff(const char *path, int32_t flags);
 void uphip_source_destroy(UphipSource *source);
 UphipSink *uphip_sink_callback(UphipStoreFn store, void *user);
 UphipSink *uphip_sink_memory(void *base, int64_t linesize, int64_t sheet_stride,

@@ -330,6 +330,7 @@ bool decode(Png& p, uint8_t* out, int64_t linesize, const char* path) {
 
 // the file's signature: 1 PNG, 2 JPEG (SOI + a marker), 3 JPEG 2000 (the JP2
 // signature box or SOC + SIZ), 4 PDF (whole documents: uphip_source_pdf),
+// 5 TIFF (either byte order; BigTIFF too, which its reader refuses by name),
 // 0 anything else (PNM)
 int sniff(FILE* f) {
   uint8_t sig[12];
@@ -342,6 +343,9 @@ int sniff(FILE* f) {
       (n >= 4 && sig[0] == 0xFF && sig[1] == 0x4F && sig[2] == 0xFF && sig[3] == 0x51))
     return 3;
   if (n >= 5 && memcmp(sig, "%PDF-", 5) == 0) return 4;
+  if (n >= 4 && ((sig[0] == 'I' && sig[1] == 'I' && (sig[2] == 42 || sig[2] == 43) && sig[3] == 0) ||
+                 (sig[0] == 'M' && sig[1] == 'M' && sig[2] == 0 && (sig[3] == 42 || sig[3] == 43))))
+    return 5;
   return 0;
 }
 
@@ -398,7 +402,7 @@ int uphip_png_read(const char* path, void* dst, int64_t linesize, const UphipPnm
 
 // loadImage's peer over the codecs: the file's signature picks PNG, JPEG
 // (entropy-decoded on the host, pixels made on the current device: jpeg.cpp),
-// JPEG 2000 (j2k.cpp, likewise split) or PNM.
+// JPEG 2000 (j2k.cpp, likewise split), TIFF (tiff.cpp, on the host) or PNM.
 int uphip_image_probe(const char* path, UphipPnmInfo* info) {
   if (!path || !info) return fail("image_probe: null argument"), -1;
   FILE* f = fopen(path, "rb");
@@ -411,6 +415,7 @@ int uphip_image_probe(const char* path, UphipPnmInfo* info) {
   return kind == 1 ? uphip_png_probe(path, info)
        : kind == 2 ? uphip_jpeg_probe(path, info)
        : kind == 3 ? uphip_jp2_probe(path, info)
+       : kind == 5 ? uphip_tiff_probe(path, info)
                    : uphip_pnm_probe(path, info);
 }
 
@@ -426,6 +431,7 @@ int uphip_image_read(const char* path, void* dst, int64_t linesize, const UphipP
   return kind == 1 ? uphip_png_read(path, dst, linesize, expect)
        : kind == 2 ? uphip_jpeg_read(path, dst, linesize, expect)
        : kind == 3 ? uphip_jp2_read(path, dst, linesize, expect)
+       : kind == 5 ? uphip_tiff_read(path, dst, linesize, expect)
                    : uphip_pnm_read(path, dst, linesize, expect);
 }
 

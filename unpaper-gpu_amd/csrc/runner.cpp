@@ -352,6 +352,7 @@ struct SlotLoop {
     if (first >= run.njobs) return jobs_left = false;
     sl->first = first;
     sl->jdev = false;
+    sl->tdev = false;
     sl->count = (int32_t)std::min<int64_t>(S, run.njobs - first);
     sl->failed.assign((size_t)sl->count, 0);
     sl->last_first = first;
@@ -362,6 +363,8 @@ struct SlotLoop {
     }
     if (sl->jpg.size() < (size_t)(sl->count * nin)) sl->jpg.resize((size_t)(sl->count * nin));
     for (JpegPage& jp : sl->jpg) jp.on = false;
+    if (sl->tif.size() < (size_t)(sl->count * nin)) sl->tif.resize((size_t)(sl->count * nin));
+    for (TiffPage& tp : sl->tif) tp.on = false;
     pend[k] = sl->count;
     state[k] = LOADING;
     phase[k] = LOADING;
@@ -374,7 +377,9 @@ struct SlotLoop {
     const auto a = Clock::now();
     for (int j = 0; j < nin; j++) {
       uint8_t* dst = sl->hin.as() + ((int64_t)s * nin + j) * r->in_page_stride;
-      if (!load_page(r, dc.device, run.src, sl->first + s, j, dst, &sl->jpg[(size_t)(s * nin + j)])) {
+      const size_t q = (size_t)(s * nin + j);
+      if (!load_page(r, dc.device, run.src, sl->first + s, j, dst, &sl->jpg[q], &sl->tif[q])) {
+        sl->jpg[q].on = sl->tif[q].on = false;
         sl->failed[(size_t)s] |= 4;
         uphip_clear_error();
         // the slot still runs: a blank (white) page, cheap and
@@ -400,7 +405,8 @@ struct SlotLoop {
                                   hipMemcpyHostToDevice, (hipStream_t)uphip_batch_stream(sl->b))) &&
            uphip_batch_run_device(sl->b, sl->count, sl->din.as(), src->linesize, src->page_stride) == 0;
     } else {
-      ok = upload_staging(r, sl, npages) && jpeg_submit(sl, npages) && uphip_batch_run(sl->b, sl->count) == 0;
+      ok = upload_staging(r, sl, npages) && jpeg_submit(sl, npages) && tiff_submit(sl, npages) &&
+           uphip_batch_run(sl->b, sl->count) == 0;
     }
     const PackedCodec* pc = packed_codec(sink);
     if (!ok || (pc && pc->encode(sl->b, sink) != 0)) return fail_chunk(k, "run failed");
@@ -414,16 +420,20 @@ struct SlotLoop {
     std::vector<char> pre = sl->failed;
     collect_failures(*sl);
     for (size_t s = 0; s < pre.size(); s++) sl->failed[s] |= pre[s];
-    if (!sl->jdev) return;
-    // pages whose entropy-coded data the device found corrupt
+    // pages whose entropy-coded data, or whose TIFF strips, the device found corrupt
     std::vector<int32_t> jst((size_t)(sl->count * nin), 0);
-    if (!UPH_HIP(hipMemcpy(jst.data(), sl->djst.as(), 4 * jst.size(), hipMemcpyDeviceToHost)))
-      jst.assign(jst.size(), 1);
-    for (size_t q = 0; q < jst.size(); q++)
-      if (jst[q]) {
-        sl->failed[q / (size_t)nin] |= 4;
-        if (dc.error.empty()) dc.error = "corrupt JPEG entropy-coded data (device decode)";
-      }
+    auto page_status = [&](bool any, const Buffer& dst, const char* what) {
+      if (!any) return;
+      if (!UPH_HIP(hipMemcpy(jst.data(), dst.as(), 4 * jst.size(), hipMemcpyDeviceToHost)))
+        jst.assign(jst.size(), 1);
+      for (size_t q = 0; q < jst.size(); q++)
+        if (jst[q]) {
+          sl->failed[q / (size_t)nin] |= 4;
+          if (dc.error.empty()) dc.error = what;
+        }
+    };
+    page_status(sl->jdev, sl->djst, "corrupt JPEG entropy-coded data (device decode)");
+    page_status(sl->tdev, sl->dtst, "corrupt TIFF strip (device decode)");
   }
 
   // A finished run: its status, then its D2H queued -- the sheets, or what

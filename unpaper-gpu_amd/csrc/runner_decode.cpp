@@ -143,21 +143,60 @@ bool pdf_load(UphipRunner* r, int device, const UphipSource* s, int64_t idx, uin
 
 size_t up256(size_t n) { return (n + 255) & ~(size_t)255; }
 
+bool is_tiff_file(const std::string& path) {
+  FILE* f = fopen(path.c_str(), "rb");
+  if (!f) return false;
+  uint8_t sig[4];
+  const bool yes = fread(sig, 1, 4, f) == 4 && ((sig[0] == 'I' && sig[1] == 'I' && sig[2] == 42 && sig[3] == 0) ||
+                                                (sig[0] == 'M' && sig[1] == 'M' && sig[2] == 0 && sig[3] == 42));
+  fclose(f);
+  return yes;
+}
+
+// Page `idx` of a TIFF document: its pixels into the staging, or, when the
+// source asks for the device route and the page qualifies, its strips into
+// the slot's pinned blob `tp` (tiff_dec.h).
+bool tiff_load(UphipRunner* r, int device, const tiff::Document& doc, int64_t idx, bool host_only, uint8_t* dst,
+               TiffPage* tp) {
+  const tiff::Page* p = tiff::page(doc, idx);
+  if (!p) return false;
+  // the geometry first: nothing is sized from a page of another shape
+  if (!same_geometry(r, UphipPnmInfo{p->width, p->height, p->format}, "tiff", doc.name.c_str())) return false;
+  if (host_only || !tiff::device_route(*p)) return tiff::decode_host(doc, *p, dst, r->in_pitch);
+  if (uphip_set_device(device) != 0) return false;
+  const size_t need = tiff::blob_bytes(*p);
+  if (!tp->host.reserve(need, need / 4)) return false;
+  tiff::blob_fill(doc, *p, tp->host.as());
+  tp->jobs.resize(p->off.size());
+  tiff::page_jobs(*p, 0, 0, 0, tp->jobs.data());
+  tp->rows = tiff::rows_page(*p, 0, 0, 0, nullptr, 0);
+  tp->raster = (uint64_t)p->src_row_bytes * (uint64_t)p->height;
+  tp->lzw = p->compression == tiff::kCompLzw;
+  tp->bytes = need;
+  tp->on = true;
+  return true;
+}
+
 constexpr int kJ2kSubBatch = 16;  // pages coded per k_j2k_t1enc launch (bounds the arena)
 
 }  // namespace
 
 bool load_page(UphipRunner* r, int device, const UphipSource* s, int64_t job, int32_t j,
-               uint8_t* dst, JpegPage* jp) {
+               uint8_t* dst, JpegPage* jp, TiffPage* tp) {
   const UphipPnmInfo geo{r->geo.page_width, r->geo.page_height, r->geo.page_format};
   const int64_t idx = job * r->opts.input_count + j;
   if (s->load) return s->load(s->user, job, j, dst, r->in_pitch) == 0;
   if (s->base) return mem_load(s, idx, dst, r->in_pitch, geo) == 0;
   if (s->pdf) return pdf_load(r, device, s, idx, dst, jp);
+  if (s->tiff) return tiff_load(r, device, *s->tiff, idx, !(s->tiff_flags & UPHIP_TIFF_DEVICE_DECODE), dst, tp);
   if (idx >= 0 && idx < (int64_t)s->paths.size()) {
     const std::string& path = s->paths[(size_t)idx];
     if (is_jpeg_file(path)) return file_load(jpeg_load_mem, r, device, path, jp);
     if (is_j2k_file(path)) return file_load(j2k_load_mem, r, device, path, jp);
+    if (is_tiff_file(path)) {
+      tiff::Document doc;
+      return tiff::open_file(path.c_str(), &doc) && tiff_load(r, device, doc, 0, true, dst, tp);
+    }
   }
   return pnm_load(s, idx, dst, r->in_pitch, geo) == 0;
 }
@@ -167,17 +206,18 @@ bool load_page(UphipRunner* r, int device, const UphipSource* s, int64_t job, in
 // other pages go as one copy each (the staging is laid out like the slots).
 bool upload_staging(UphipRunner* r, Slot* sl, int npages) {
   bool any = false;
-  for (int p = 0; p < npages; p++) any |= sl->jpg[(size_t)p].on;
+  auto on = [sl](int p) { return sl->jpg[(size_t)p].on || sl->tif[(size_t)p].on; };
+  for (int p = 0; p < npages; p++) any |= on(p);
   if (!any)
     return uphip_batch_upload_async(sl->b, sl->count, sl->hin.as(), r->in_pitch, r->in_page_stride) == 0;
   hipStream_t st = (hipStream_t)uphip_batch_stream(sl->b);
   for (int p = 0; p < npages;) {
-    if (sl->jpg[(size_t)p].on) {
+    if (on(p)) {
       p++;
       continue;
     }
     int e = p;
-    while (e < npages && !sl->jpg[(size_t)e].on) e++;
+    while (e < npages && !on(e)) e++;
     int64_t pitch = 0;
     uint8_t* dst = (uint8_t*)uphip_batch_input_ptr(sl->b, p, &pitch);
     if (!dst || pitch != r->in_pitch ||
@@ -315,6 +355,67 @@ bool jpeg_submit(Slot* sl, int npages) {
     off += up256(jp.bytes);
   }
   return true;
+}
+
+// Queue the chunk's device-route TIFF pages on the slot's stream: one upload
+// per blob, the jobs and page records of all of them (offsets made
+// chunk-wide), then one launch of the strips and one of the rows into the
+// pages' input slots (after the staging upload, before the run).
+bool tiff_submit(Slot* sl, int npages) {
+  size_t in_bytes = 0, njobs = 0, npg = 0;
+  uint64_t raster = 0;
+  bool lzw = false;
+  int maxh = 0;
+  sl->tdev = false;
+  for (int p = 0; p < npages; p++) {
+    const TiffPage& tp = sl->tif[(size_t)p];
+    if (!tp.on) continue;
+    in_bytes += up256(tp.bytes);
+    njobs += tp.jobs.size();
+    raster += (tp.raster + 255) & ~(uint64_t)255;
+    lzw |= tp.lzw;
+    maxh = std::max(maxh, tp.rows.height);
+    npg++;
+  }
+  if (!npg) return true;
+  const size_t jb = up256(sizeof(tiff::StripJob) * njobs), rb = up256(sizeof(tiff::RowsPage) * npg);
+  auto grow = [](Buffer& b, size_t need) { return b.reserve(need, need / 4); };
+  if (!grow(sl->dtif, in_bytes + jb + rb) || !grow(sl->htif, jb + rb) || !grow(sl->dtsc, (size_t)raster) ||
+      !grow(sl->dtst, 4 * (size_t)npages) ||
+      (lzw && !sl->dtpl.reserve((size_t)tiff::strip_lanes((int64_t)njobs) * tiff::kTableBytes)))
+    return false;
+  hipStream_t st = (hipStream_t)uphip_batch_stream(sl->b);
+  sl->tdev = true;
+  tiff::StripJob* hj = sl->htif.as<tiff::StripJob>();
+  tiff::RowsPage* hr = (tiff::RowsPage*)(sl->htif.as() + jb);
+  uint8_t* const din = sl->dtif.as();
+  size_t io = 0, q = 0, k = 0;
+  uint64_t so = 0;
+  for (int p = 0; p < npages; p++) {
+    const TiffPage& tp = sl->tif[(size_t)p];
+    if (!tp.on) continue;
+    if (!UPH_HIP(hipMemcpyAsync(din + io, tp.host.as(), tp.bytes, hipMemcpyHostToDevice, st))) return false;
+    for (tiff::StripJob j : tp.jobs) {
+      j.in_off += io;
+      j.out_off += so;
+      j.page = p;
+      hj[q++] = j;
+    }
+    tiff::RowsPage rp = tp.rows;
+    rp.src_off += so;
+    rp.pal_off += io;
+    rp.page = p;
+    rp.dst = (uint8_t*)uphip_batch_input_ptr(sl->b, p, &rp.pitch);
+    if (!rp.dst) return false;
+    hr[k++] = rp;
+    io += up256(tp.bytes);
+    so += (tp.raster + 255) & ~(uint64_t)255;
+  }
+  return UPH_HIP(hipMemcpyAsync(din + in_bytes, sl->htif.as(), jb + rb, hipMemcpyHostToDevice, st)) &&
+         UPH_HIP(hipMemsetAsync(sl->dtst.as(), 0, 4 * (size_t)npages, st)) &&
+         tiff::launch((const tiff::StripJob*)(din + in_bytes), (int)njobs, lzw,
+                      (const tiff::RowsPage*)(din + in_bytes + jb), (int)npg, maxh, din, in_bytes, sl->dtsc.as(),
+                      raster, sl->dtpl.as<uint16_t>(), sl->dtst.as<int32_t>(), st);
 }
 
 // The chunk's output pages as lossless JPEG 2000 code-blocks, queued on the

@@ -21,6 +21,7 @@
 #include "jpeg.h"
 #include "pdf.h"
 #include "runtime.h"
+#include "tiff_dec.h"
 
 namespace uph {
 
@@ -67,6 +68,9 @@ struct UphipSource {
   // a PDF document: page i of it is input page i (uphip_source_pdf)
   std::shared_ptr<uph::pdf::Document> pdf;
   int32_t pdf_dpi = 0;
+  // a multi-page TIFF: IFD i of it is input page i (uphip_source_tiff)
+  std::shared_ptr<uph::tiff::Document> tiff;
+  int32_t tiff_flags = 0;
   uph::HostRegistration reg;
 };
 
@@ -121,8 +125,30 @@ struct JpegPage {
   int maxw = 0, maxh = 0;
 };
 
+// A TIFF page of a chunk on the device route (tiff_dec.h): a load task
+// leaves its blob (the strips' bytes, the palette) and its jobs (offsets
+// relative to the page) in pinned memory; the device thread uploads the
+// chunk's blobs and decodes all their strips in one launch on the slot's
+// stream, then finishes the rows into the batch's input slots.
+struct TiffPage {
+  Buffer host{Buffer::Pinned};  // the blob; grown on demand
+  bool on = false;              // this chunk's page waits for the device
+  size_t bytes = 0;             // of the blob
+  std::vector<tiff::StripJob> jobs;
+  tiff::RowsPage rows{};
+  uint64_t raster = 0;          // the page as stored: its share of the scratch
+  bool lzw = false;
+};
+
 struct Slot {
   std::vector<JpegPage> jpg;     // per page of the chunk (sheet * input_count + page)
+  std::vector<TiffPage> tif;     // likewise
+  Buffer dtif{Buffer::Device};   // the chunk's TIFF blobs, then its jobs and page records
+  Buffer htif{Buffer::Pinned};   // the jobs and page records, offsets made chunk-wide
+  Buffer dtsc{Buffer::Device};   // the decoded strips (every TIFF page as stored)
+  Buffer dtpl{Buffer::Device};   // the LZW tables of k_tiff_strips' lanes (at most 64 MiB)
+  Buffer dtst{Buffer::Device};   // per page: strip decode status (int32_t)
+  bool tdev = false;             // the chunk has device-decoded TIFF pages (statuses to read)
   Buffer djpg{Buffer::Device};   // device copies of the chunk's packed JPEG pages
   Buffer hj2j{Buffer::Pinned};   // the chunk's JPEG 2000 jobs (j2k::T1Job), offsets made chunk-wide
   Buffer dj2j{Buffer::Device};   // their device copy
@@ -224,9 +250,10 @@ bool sink_write(const UphipSink* k, int64_t idx, const uint8_t* p, size_t n, int
 
 // runner_decode.cpp
 bool load_page(UphipRunner* r, int device, const UphipSource* s, int64_t job, int32_t j, uint8_t* dst,
-               JpegPage* jp);
+               JpegPage* jp, TiffPage* tp);
 bool upload_staging(UphipRunner* r, Slot* sl, int npages);
 bool jpeg_submit(Slot* sl, int npages);
+bool tiff_submit(Slot* sl, int npages);
 bool jp2_chunk_submit(UphipRunner* r, Slot* sl, int npg);
 
 }  // namespace uph

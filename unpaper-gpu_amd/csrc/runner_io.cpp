@@ -194,9 +194,23 @@ UphipSource* uphip_source_pdf(const char* path, int32_t dpi) {
   return s;
 }
 
+UphipSource* uphip_source_tiff(const char* path, int32_t flags) {
+  if (!path) return fail("source_tiff: null path"), nullptr;
+  if ((flags & ~(UPHIP_TIFF_HOST_DECODE | UPHIP_TIFF_DEVICE_DECODE)) ||
+      flags == (UPHIP_TIFF_HOST_DECODE | UPHIP_TIFF_DEVICE_DECODE))
+    return fail("source_tiff: flags %d", flags), nullptr;
+  auto doc = std::make_shared<tiff::Document>();
+  if (!tiff::open_file(path, doc.get())) return nullptr;
+  UphipSource* s = new UphipSource();
+  s->tiff = std::move(doc);
+  s->tiff_flags = flags;
+  return s;
+}
+
 int64_t uphip_source_page_count(UphipSource* s) {
   if (!s) return fail("source_page_count: null source"), -1;
   if (s->pdf) return s->pdf->page_count();
+  if (s->tiff) return (int64_t)s->tiff->pages.size();
   if (s->base) return s->npages;
   if (!s->paths.empty()) return (int64_t)s->paths.size();
   return fail("source_page_count: a callback source has no page count"), -1;

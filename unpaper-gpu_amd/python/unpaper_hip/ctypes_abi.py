@@ -211,6 +211,8 @@ class PnmInfo(C.Structure):
 
 
 RUNNER_MAX_DEVICES = 16
+TIFF_HOST_DECODE = 1            # uphip_source_tiff flags
+TIFF_DEVICE_DECODE = 2
 
 
 class RunnerConfig(C.Structure):

@@ -72,6 +72,9 @@ EXPORTED = [
     "uphip_png_encode_host", "uphip_png_encode", "uphip_png_wrap", "uphip_batch_encode_png_async",
     "uphip_batch_png_sizes", "uphip_batch_png_download_async", "uphip_pdf_writer_add_page_flate",
     "uphip_sink_png", "uphip_sink_pdf_lossless",
+    "uphip_tiff_probe", "uphip_tiff_read", "uphip_tiff_open", "uphip_tiff_close",
+    "uphip_tiff_page_count", "uphip_tiff_page_probe", "uphip_tiff_read_page",
+    "uphip_tiff_page_on_device", "uphip_tiff_decode", "uphip_source_tiff",
 ]
 
 
@@ -294,6 +297,19 @@ def load_library(path=LIB_PATH):
                                                       C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
         "uphip_sink_png": (C.c_void_p, [C.c_char_p, C.c_int64, C.c_int32]),
         "uphip_sink_pdf_lossless": (C.c_void_p, [C.c_char_p, C.POINTER(A.PdfMetadata), C.c_int32]),
+        "uphip_tiff_probe": (C.c_int, [C.c_char_p, C.POINTER(A.PnmInfo)]),
+        "uphip_tiff_read": (C.c_int, [C.c_char_p, C.c_void_p, C.c_int64, C.POINTER(A.PnmInfo)]),
+        "uphip_tiff_open": (C.c_void_p, [C.c_char_p]),
+        "uphip_tiff_close": (None, [C.c_void_p]),
+        "uphip_tiff_page_count": (C.c_int, [C.c_void_p]),
+        "uphip_tiff_page_probe": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(A.PnmInfo),
+                                            C.POINTER(C.c_float)]),
+        "uphip_tiff_read_page": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64,
+                                           C.POINTER(A.PnmInfo)]),
+        "uphip_tiff_page_on_device": (C.c_int, [C.c_void_p, C.c_int]),
+        "uphip_tiff_decode": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p, C.c_int64,
+                                        C.POINTER(A.PnmInfo)]),
+        "uphip_source_tiff": (C.c_void_p, [C.c_char_p, C.c_int32]),
     }
     for name, (res, args) in sig.items():
         if not hasattr(L, name):

@@ -393,6 +393,77 @@ def source_pdf(path, dpi=0):
     return _Handle(h, L.uphip_source_destroy)
 
 
+def source_tiff(path, flags=0):
+    """IFD i of a TIFF as input page i (uphip_source_tiff; flags:
+    ctypes_abi.TIFF_DEVICE_DECODE sends the pages that qualify through the
+    device decode, TIFF_HOST_DECODE or 0 every page to the load tasks)."""
+    L = load_library()
+    h = L.uphip_source_tiff(path.encode(), flags)
+    _check(L)
+    if not h:
+        raise UnpaperHipError("source_tiff failed")
+    return _Handle(h, L.uphip_source_destroy)
+
+
+class TiffDocument:
+    """A TIFF file, one page per IFD (uphip_tiff_open)."""
+
+    def __init__(self, path):
+        self.lib = L = load_library()
+        self.handle = L.uphip_tiff_open(path.encode())
+        if not self.handle:
+            _check(L)
+            raise UnpaperHipError("tiff_open failed")
+
+    @property
+    def page_count(self):
+        return self.lib.uphip_tiff_page_count(self.handle)
+
+    def probe(self, page):
+        """(width, height, format, (x dpi, y dpi))"""
+        info, dpi = A.PnmInfo(), (C.c_float * 2)()
+        if self.lib.uphip_tiff_page_probe(self.handle, page, C.byref(info), dpi) != 0:
+            _check(self.lib)
+        return info.width, info.height, info.format, (dpi[0], dpi[1])
+
+    def on_device(self, page):
+        r = self.lib.uphip_tiff_page_on_device(self.handle, page)
+        if r < 0:
+            _check(self.lib)
+        return r == 1
+
+    def read_page(self, page) -> HostImage:
+        w, h, fmt, _ = self.probe(page)
+        img = HostImage(w, h, fmt)
+        if self.lib.uphip_tiff_read_page(self.handle, page, img.data.ctypes.data, img.linesize,
+                                         None) != 0:
+            _check(self.lib)
+        return img
+
+    def close(self):
+        if self.handle:
+            self.lib.uphip_tiff_close(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def tiff_decode(data: bytes, page, device_ptr, pitch):
+    """Page `page` of a TIFF file image decoded on the device into device_ptr
+    (uphip_tiff_decode); returns (width, height, format)."""
+    L = load_library()
+    info = A.PnmInfo(0, 0, 0)
+    buf = (C.c_uint8 * len(data)).from_buffer_copy(data)
+    if L.uphip_tiff_decode(buf, len(data), page, device_ptr, pitch, C.byref(info)) != 0:
+        _check(L)
+        raise UnpaperHipError("tiff_decode failed")
+    return info.width, info.height, info.format
+
+
 def source_page_count(src):
     L = load_library()
     n = L.uphip_source_page_count(src.handle)
