@@ -12,6 +12,9 @@
 #   make sanitize_tiff -> tests/c/_build/tiff_main: the TIFF reader (container
 #                      and strip decoder, the device kernels' host twin) under
 #                      ASan/UBSan over the files of a directory, stand-alone
+#   make sanitize_tiff_enc -> tests/c/_build/tiff_enc_main: the TIFF encoder's
+#                      host twin and the container writer under ASan/UBSan,
+#                      read back through the TIFF reader, stand-alone
 #   make lib DIAG=1 -> the same library with the timing diagnostics of
 #                      csrc/common.h (UPHIP_DIAG_*) compiled in; tuning only,
 #                      built into its own object dir.  The default build has none.
@@ -67,7 +70,7 @@ LLVMCC     := /opt/rocm/lib/llvm/bin/clang
 SANFLAGS   := -fsanitize=address,undefined -fno-sanitize-recover=undefined \
               -fno-omit-frame-pointer -g -O1
 
-.PHONY: all lib oracle ctest sanitize sanitize_png sanitize_tiff libm_check jdec_emul j2k_emul clean
+.PHONY: all lib oracle ctest sanitize sanitize_png sanitize_tiff sanitize_tiff_enc libm_check jdec_emul j2k_emul clean
 all: lib oracle ctest libm_check jdec_emul j2k_emul
 
 lib: $(LIB)
@@ -182,6 +185,19 @@ $(TIFF_MAIN): tests/c/tiff_main.cpp $(CSRC)/tiff.cpp $(CSRC)/ccitt.cpp $(HDRS)
 
 sanitize_tiff: $(TIFF_MAIN)
 	ASAN_OPTIONS=detect_leaks=1 UBSAN_OPTIONS=print_stacktrace=1 $(TIFF_MAIN) $(TIFF_DIR)
+
+# the TIFF encoder's host twin and the container writer with their own main:
+# every case encoded, written into one multi-page file and read back through
+# the TIFF reader; no device code
+TIFF_ENC_MAIN := tests/c/_build/tiff_enc_main
+TIFF_ENC_SRCS := tests/c/tiff_enc_main.cpp $(CSRC)/tiff_write.cpp $(CSRC)/png_enc.cpp $(CSRC)/tiff.cpp $(CSRC)/ccitt.cpp
+$(TIFF_ENC_MAIN): $(TIFF_ENC_SRCS) $(HDRS)
+	@mkdir -p tests/c/_build
+	$(HIPCC) --cuda-host-only -x hip $(SANFLAGS) -std=c++17 -Wall -Wno-unused-function -Wno-unused-result \
+	  -Wno-unused-value -Iinclude -I$(CSRC) $(TIFF_ENC_SRCS) -o $@ -lz
+
+sanitize_tiff_enc: $(TIFF_ENC_MAIN)
+	ASAN_OPTIONS=detect_leaks=1 UBSAN_OPTIONS=print_stacktrace=1 $(TIFF_ENC_MAIN)
 
 clean:
 	rm -rf $(PKG)/build $(PKG)/build_diag $(PKG)/lib $(PKG)/lib_diag oracle/_build oracle/_ref tests/c/_build

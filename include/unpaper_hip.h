@@ -502,11 +502,26 @@ int uphip_batch_g4_download_async(UphipBatch *batch, void *host, int64_t capacit
 int uphip_batch_encode_png_async(UphipBatch *batch);
 int64_t uphip_batch_png_sizes(UphipBatch *batch, int64_t *sizes, int32_t max_pages);
 int uphip_batch_png_download_async(UphipBatch *batch, void *host, int64_t capacity);
+/* The TIFF output branch for a whole batch, the peer of the PNG three for
+ * batches whose output format is GRAY8 or RGB24 (a Y400A batch leaves as
+ * GRAY8; bilevel sheets take the Group 4 three): every output page of the
+ * last run as the packed page of uphip_tiff_encode (its StripByteCounts,
+ * then its Deflate strips), the pages one after another in device memory.
+ *   tiff_sizes:           sizes[i] of page i (always > 0: a strip that would
+ *                         not shrink goes out stored); returns the total
+ *   tiff_download_async:  the packed pages into host memory (total bytes);
+ *                         uphip_tiff_writer_add_page_deflate takes each.
+ * The encode buffers are allocated by the first encode and counted by
+ * uphip_batch_device_bytes from then on. */
+int uphip_batch_encode_tiff_async(UphipBatch *batch);
+int64_t uphip_batch_tiff_sizes(UphipBatch *batch, int64_t *sizes, int32_t max_pages);
+int uphip_batch_tiff_download_async(UphipBatch *batch, void *host, int64_t capacity);
 /* Row pitch of the output sheets on the device: host staging with this
  * linesize (and pitch * height per sheet) downloads as linear DMA copies. */
 int uphip_batch_output_pitch(UphipBatch *batch, int64_t *pitch);
 /* Device memory the batch holds (planes, inputs, scratch, tables, and the
- * buffers of the lossless encoder once uphip_batch_encode_png_async ran). */
+ * buffers of the lossless encoders once uphip_batch_encode_png_async or
+ * uphip_batch_encode_tiff_async ran). */
 int uphip_batch_device_bytes(UphipBatch *batch, int64_t *bytes);
 
 /* ---------------------------------------------------------------------------
@@ -658,6 +673,71 @@ int64_t uphip_png_encode(const void *device_src, int64_t pitch, int32_t offset, 
  * included.  Sizes and errors as uphip_png_encode.  No reference peer. */
 int64_t uphip_png_wrap(const void *stream, int64_t len, int32_t width, int32_t height,
                        int32_t format, int32_t dpi, void *out, int64_t capacity);
+/* Lossless TIFF encode (no reference peer).  GRAY8 -> 1 sample, Photometric
+ * 1; RGB24 -> 3 samples, Photometric 2; Y400A -> gray and one ExtraSamples 2
+ * sample; all Compression 8 (Deflate) with Predictor 2, in strips of
+ * RowsPerStrip = clamp(65536 / row bytes, 1, height) rows, each strip a zlib
+ * stream of its own: one dynamic-Huffman block over the deterministic LZ77
+ * parse of the PNG encoder restarted at the strip (csrc/tiff_enc_core.h), or
+ * stored blocks when that would not be smaller.  MONOWHITE -> the Group 4
+ * file of uphip_tiff_g4_write (`offset`: the bit of a row that holds pixel
+ * 0; it must be 0 for the byte formats).  MONOBLACK is refused.  The result
+ * is a whole classic little-endian file of one page: header, the page's
+ * data, its IFD (dpi 0 = 300).  Returns the file's size; out = NULL sizes a
+ * buffer; -1 on error (also when `capacity` is too small).
+ *   uphip_tiff_encode_host: rows `stride` apart in host memory; needs no device.
+ *   uphip_tiff_encode:      rows `pitch` apart in device memory, coded on the
+ *                           current device to the same bytes; synchronous.
+ *   uphip_tiff_encode_pages: `npages` byte-format pages `page_stride` apart in
+ *                           device memory as their packed pages (the
+ *                           StripByteCounts as little-endian uint32, then the
+ *                           strips), one after another; sizes[i] (may be
+ *                           NULL) gets page i's size, the total is returned.
+ *                           `fold`: the most (page, strip) streams a launch
+ *                           puts on its grid's y axis, 0 = 65535; a block
+ *                           takes every fold-th stream.  device_out (may be
+ *                           NULL): device memory on a 4-byte boundary that
+ *                           the encoder packs the pages into instead of a
+ *                           buffer of its own; it zeroes and writes only the
+ *                           first B bytes, B = the pages' bound (per page 4
+ *                           bytes a strip + every strip stored: n + 5 *
+ *                           ceil(n / 65535) + 6 for n bytes) rounded up to
+ *                           a multiple of 4, + 4, and fails when
+ *                           device_capacity is less.  Test and tooling
+ *                           entry. */
+int64_t uphip_tiff_encode_host(const void *pixels, int64_t stride, int32_t offset, int32_t width,
+                               int32_t height, int32_t format, int32_t dpi, void *out,
+                               int64_t capacity);
+int64_t uphip_tiff_encode(const void *device_src, int64_t pitch, int32_t offset, int32_t width,
+                          int32_t height, int32_t format, int32_t dpi, void *out, int64_t capacity);
+int64_t uphip_tiff_encode_pages(const void *device_src, int64_t pitch, int64_t page_stride,
+                                int32_t npages, int32_t width, int32_t height, int32_t format,
+                                int32_t fold, int64_t *sizes, void *out, int64_t capacity,
+                                void *device_out, int64_t device_capacity);
+/* A TIFF of many pages, the peer of the uphip_pdf_writer_* entries: classic,
+ * little-endian, one IFD per page.  add_page_* may be called from several
+ * threads in any order: `index` orders the pages in the file (-1: after the
+ * highest so far); a page's data is appended at once, finish writes the IFDs
+ * after the data, chained in index order with PageNumber counted over the
+ * pages present, and gives the file its name (until then it is path.part).
+ * A file of one page has the bytes of uphip_tiff_encode.  A page that would
+ * put an offset at or beyond 2^32 - 1 is refused with an error naming the
+ * 4 GiB limit of classic TIFF; the pages before it stay.  dpi 0 = the
+ * writer's, whose 0 = 300.  close frees the writer; unfinished, it leaves no
+ * file.  0 / -1.
+ *   add_page_deflate: a packed page of uphip_tiff_encode_pages /
+ *                     uphip_batch_tiff_download_async (GRAY8, RGB24, Y400A)
+ *   add_page_g4:      a Group 4 stream (uphip_g4_encode), one strip, the tags
+ *                     of uphip_tiff_g4_write */
+typedef struct UphipTiffWriter UphipTiffWriter;
+UphipTiffWriter *uphip_tiff_writer_open(const char *path, int32_t dpi);
+int uphip_tiff_writer_add_page_deflate(UphipTiffWriter *w, int64_t index, const uint8_t *page,
+                                       size_t len, int32_t width, int32_t height, int32_t format,
+                                       int32_t dpi);
+int uphip_tiff_writer_add_page_g4(UphipTiffWriter *w, int64_t index, const uint8_t *data, size_t len,
+                                  int32_t width, int32_t height, int32_t dpi);
+int uphip_tiff_writer_finish(UphipTiffWriter *w);
+void uphip_tiff_writer_close(UphipTiffWriter *w);
 /* TIFF third of loadImage (file.c:29-131; the reference reads TIFF through
  * FFmpeg), without libtiff.  Classic TIFF of either byte order, strips,
  * PlanarConfiguration 1; 1-bit Photometric 0 -> MONOWHITE and 1 -> MONOBLACK
@@ -955,6 +1035,22 @@ UphipSink *uphip_sink_pdf_bilevel(const char *path, const UphipPdfMetadata *meta
  *                            output_pixel_format. */
 UphipSink *uphip_sink_png(const char *pattern, int64_t wrap, int32_t dpi);
 UphipSink *uphip_sink_pdf_lossless(const char *path, const UphipPdfMetadata *meta, int32_t dpi);
+/* TIFF output in the runner's output format, coded on the device right after
+ * the batch: Group 4 pages (as uphip_sink_tiff_g4) when the sheets leave as
+ * MONOWHITE, Deflate strips with Predictor 2 (uphip_tiff_encode) when they
+ * leave as GRAY8 or RGB24 (a Y400A batch leaves as GRAY8).  The sink holds no
+ * format: the codec is chosen from the runner's output format wherever the
+ * runner asks for the sink's codec.  (No batch leaves as MONOBLACK: a
+ * bilevel output_pixel_format is saved as MONOWHITE.)  dpi 0 = 300.
+ *   uphip_sink_tiff:           one TIFF per output page; names as
+ *                              uphip_sink_pnm.
+ *   uphip_sink_tiff_multipage: one TIFF of all output pages
+ *                              (uphip_tiff_writer_*): pages in output order,
+ *                              failed ones left out; uphip_sink_finish
+ *                              completes the file (0 / -1); destroyed
+ *                              unfinished it leaves no file. */
+UphipSink *uphip_sink_tiff(const char *pattern, int64_t wrap, int32_t dpi);
+UphipSink *uphip_sink_tiff_multipage(const char *path, int32_t dpi);
 int uphip_sink_finish(UphipSink *sink);
 void uphip_sink_destroy(UphipSink *sink);
 

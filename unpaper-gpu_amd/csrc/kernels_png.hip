@@ -9,6 +9,7 @@
 
 #include "png_enc.h"
 #include "png_enc_core.h"
+#include "png_enc_dev.h"
 #include "runtime.h"
 #include "unpaper_hip.h"
 
@@ -22,27 +23,6 @@ constexpr int kThreads = 256;                    // per block: 4 waves; a lane p
 constexpr int kFilterRows = 16;                  // rows a filter block takes at most
 constexpr uint32_t kFilterLdsAim = 16u << 10;    // LDS a filter block takes when more than one row fits
 constexpr uint32_t kLdsLimit = 160u << 10;       // the CU's LDS (allow_dynamic_lds)
-
-// A staged row: the aligned dwords that hold it, read as bytes.
-struct LdsRow {
-  const uint8_t* p;
-  __device__ uint32_t byte(int64_t i) const { return p[i]; }
-};
-
-// The byte that holds pixel 0 of row `row` of page p and the pixel's bit in it.
-__device__ inline const uint8_t* row_start(const PngPages& pg, const Shape& s, int p, int row, int* bit) {
-  const int sheet = p / pg.per_sheet;
-  const int j = p - sheet * pg.per_sheet;
-  const int plane = pg.cur ? (pg.cur[(int64_t)sheet * pg.cur_step] & 1) : 0;
-  const int64_t px = (int64_t)pg.offset + (int64_t)j * pg.sheet_width / pg.per_sheet;
-  const uint8_t* r = pg.plane[plane] + sheet * pg.sheet_stride + (int64_t)row * pg.pitch;
-  if (s.depth == 8) {
-    *bit = 0;
-    return r + px * s.channels;
-  }
-  *bit = (int)(px & 7);
-  return r + (px >> 3);
-}
 
 // Block (x, y): rows [x * R, x * R + R) of page y.  LDS: R + 1 rows of
 // `stride` words, row -1 of the block first (zeros above the page).
@@ -99,19 +79,6 @@ __global__ __launch_bounds__(kThreads) void k_png_filter(PngPages pg, Shape s, i
     filter_row(cur, off, up, up_off, row > 0, s, f, lane, 64, dst);
   }
 }
-
-struct LdsHist {
-  uint32_t* h;
-  __device__ void literal(uint32_t b) { atomicAdd(h + b, 1u); }
-  __device__ void match(int len, int dist) {
-    int sym, eb;
-    uint32_t ev;
-    length_symbol(len, &sym, &eb, &ev);
-    atomicAdd(h + sym, 1u);
-    distance_symbol(dist, &sym, &eb, &ev);
-    atomicAdd(h + kLL + sym, 1u);
-  }
-};
 
 // Lane g of page y: segment g's tokens into the block's histogram, flushed
 // to the page's counts; the segment's Adler sums.
@@ -248,35 +215,6 @@ __global__ void k_png_offsets(const int64_t* sizes, int64_t* offs, int n) {
   }
 }
 
-// Writes bits LSB first from bit `at` of the zeroed stream `out` on.  Words
-// that lie wholly inside the lane's bits are stored; the first word and the
-// last, partial one are shared with the neighbours and merged with atomicOr.
-struct EmitSink {
-  uint32_t* out;
-  int64_t w;     // word being filled
-  uint64_t acc;  // its bits and the next word's
-  int n;         // bits in acc (the first word's bits before `at` count as zeros)
-  bool first = true;
-  __device__ EmitSink(uint32_t* o, int64_t at) : out(o), w(at >> 5), acc(0), n((int)(at & 31)) {}
-  __device__ void put(uint32_t bits, int len) {
-    acc |= (uint64_t)bits << n;
-    n += len;
-    if (n >= 32) {
-      if (first)
-        atomicOr(out + w, (uint32_t)acc);
-      else
-        out[w] = (uint32_t)acc;
-      first = false;
-      w++;
-      acc >>= 32;
-      n -= 32;
-    }
-  }
-  __device__ void finish() {
-    if (n > 0) atomicOr(out + w, (uint32_t)acc);
-  }
-};
-
 // Lane g of page y writes segment g's codes; the page's first lane the
 // headers before them, its last lane what ends the stream after them.
 __global__ __launch_bounds__(kThreads) void k_png_emit(Shape s, const uint8_t* filt, int64_t filt_stride, int64_t nseg,
@@ -366,6 +304,10 @@ bool png_plan(const Shape& s, PngLaunch* l) {
   return true;
 }
 
+void png_table_launch(PageTab* tabs, unsigned n, hipStream_t st) {
+  hipLaunchKernelGGL(k_png_table, dim3(n), dim3(64), 0, st, tabs);
+}
+
 PngContext::~PngContext() { if (device >= 0) hipSetDevice(device); }
 
 bool PngContext::encode_async(const PngPages& pg, hipStream_t st) {
@@ -410,7 +352,7 @@ bool PngContext::encode_async(const PngPages& pg, hipStream_t st) {
                      l.lds_bytes, st, pg, s, l.rows, l.stride_words, filt, filt_stride);
   hipLaunchKernelGGL(k_png_hist, walk, dim3(kThreads), 0, st, s, (const uint8_t*)filt, filt_stride, nseg, tabs,
                      segadler);
-  hipLaunchKernelGGL(k_png_table, dim3(pages), dim3(64), 0, st, tabs);
+  png_table_launch(tabs, pages, st);
   hipLaunchKernelGGL(k_png_count, walk, dim3(kThreads), 0, st, s, (const uint8_t*)filt, filt_stride, nseg,
                      (const PageTab*)tabs, segoff);
   hipLaunchKernelGGL(k_png_scan, dim3(pages), dim3(kThreads), 0, st, s.total, nseg, segoff,

@@ -97,6 +97,7 @@ void uphip_batch_destroy(UphipBatch* b) {
   delete b->jenc;
   delete b->g4;
   delete b->png;
+  delete b->tiffenc;
   if (b->st) hipStreamDestroy(b->st);
   delete b;
 }
@@ -113,7 +114,8 @@ int uphip_batch_output_info(UphipBatch* b, int32_t* width, int32_t* height, int3
 
 int uphip_batch_device_bytes(UphipBatch* b, int64_t* bytes) {
   if (!b || !bytes) return fail("batch_device_bytes: null argument"), -1;
-  *bytes = (int64_t)(b->dev_bytes + (b->png ? b->png->device_bytes() : 0));
+  *bytes = (int64_t)(b->dev_bytes + (b->png ? b->png->device_bytes() : 0) +
+                     (b->tiffenc ? b->tiffenc->device_bytes() : 0));
   return 0;
 }
 
@@ -387,23 +389,25 @@ int uphip_batch_g4_download_async(UphipBatch* b, void* host, int64_t capacity) {
 }
 
 // ---- lossless output branch: PNG / Flate (png_enc.h) ----------------------
+// The output pages of the last run as the lossless encoders address them.
+static PngPages output_pages(const UphipBatch* b) {
+  const int oc = out_pages(b);
+  const int32_t pw = b->out_w / oc;
+  if (b->out)
+    return PngPages{{b->out, nullptr}, nullptr, 0, b->out_stride, b->out_pitch, oc, b->out_w, 0,
+                    (int32_t)b->out_fmt, pw, b->out_h, b->last_count * oc};
+  // the sheets lie in the plane their ctl names (as uphip_batch_download_async)
+  return PngPages{{b->planes[0], b->planes[1]}, &b->ctl[0].cur, (int64_t)(sizeof(SheetCtl) / sizeof(int32_t)),
+                  b->plane_stride, b->pitch, oc, b->out_w, 0, (int32_t)b->out_fmt, pw, b->out_h,
+                  b->last_count * oc};
+}
+
 int uphip_batch_encode_png_async(UphipBatch* b) {
   if (!b || b->last_count <= 0) return fail("batch_encode_png: nothing to encode"), -1;
   hipSetDevice(b->device);
-  const int oc = out_pages(b);
-  const int32_t pw = b->out_w / oc;
-  if (pw <= 0) return fail("batch_encode_png: empty pages"), -1;
+  const PngPages pg = output_pages(b);
+  if (pg.width <= 0) return fail("batch_encode_png: empty pages"), -1;
   if (!b->png) b->png = new PngContext();
-  PngPages pg;
-  if (b->out) {
-    pg = PngPages{{b->out, nullptr}, nullptr, 0, b->out_stride, b->out_pitch, oc, b->out_w, 0,
-                  (int32_t)b->out_fmt, pw, b->out_h, b->last_count * oc};
-  } else {
-    // the sheets lie in the plane their ctl names (as uphip_batch_download_async)
-    pg = PngPages{{b->planes[0], b->planes[1]}, &b->ctl[0].cur, (int64_t)(sizeof(SheetCtl) / sizeof(int32_t)),
-                  b->plane_stride, b->pitch, oc, b->out_w, 0, (int32_t)b->out_fmt, pw, b->out_h,
-                  b->last_count * oc};
-  }
   if (!b->png->encode_async(pg, b->st)) return -1;
   b->png_pages = pg.npages;
   return 0;
@@ -417,6 +421,31 @@ int64_t uphip_batch_png_sizes(UphipBatch* b, int64_t* sizes, int32_t max_pages) 
 int uphip_batch_png_download_async(UphipBatch* b, void* host, int64_t capacity) {
   const int64_t total = uphip_batch_png_sizes(b, nullptr, 0);
   return total < 0 ? -1 : packed_download(b, total, b->png->out.as(), host, capacity, "png");
+}
+
+// ---- TIFF output branch: Deflate strips (tiff_enc.h) -----------------------
+int uphip_batch_encode_tiff_async(UphipBatch* b) {
+  if (!b || b->last_count <= 0) return fail("batch_encode_tiff: nothing to encode"), -1;
+  if (b->out_fmt != F_GRAY8 && b->out_fmt != F_RGB24)
+    return fail("batch_encode_tiff: the batch's output format is %d, Deflate strips code GRAY8 and RGB24 sheets "
+                "(bilevel sheets take uphip_batch_encode_g4_async)", b->out_fmt), -1;
+  hipSetDevice(b->device);
+  const PngPages pg = output_pages(b);
+  if (pg.width <= 0) return fail("batch_encode_tiff: empty pages"), -1;
+  if (!b->tiffenc) b->tiffenc = new TiffEncContext();
+  if (!b->tiffenc->encode_async(pg, b->st)) return -1;
+  b->tiff_pages = pg.npages;
+  return 0;
+}
+
+int64_t uphip_batch_tiff_sizes(UphipBatch* b, int64_t* sizes, int32_t max_pages) {
+  return packed_sizes(b, b && b->tiffenc ? b->tiffenc->host_sizes.as<int64_t>() : nullptr, b ? b->tiff_pages : 0,
+                      false, "tiff", sizes, max_pages);
+}
+
+int uphip_batch_tiff_download_async(UphipBatch* b, void* host, int64_t capacity) {
+  const int64_t total = uphip_batch_tiff_sizes(b, nullptr, 0);
+  return total < 0 ? -1 : packed_download(b, total, b->tiffenc->out.as(), host, capacity, "tiff");
 }
 
 int uphip_batch_set_timing(UphipBatch* b, int32_t enable) {

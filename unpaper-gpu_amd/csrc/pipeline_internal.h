@@ -13,6 +13,7 @@
 #include "g4_enc.h"
 #include "jpeg_enc.h"
 #include "png_enc.h"
+#include "tiff_enc.h"
 #include "runtime.h"
 #include "sheet_sizes.h"
 
@@ -213,6 +214,9 @@ struct UphipBatch {
   // lossless output branch (uphip_batch_encode_png_async)
   uph::PngContext* png = nullptr;
   int png_pages = 0;
+  // TIFF output branch (uphip_batch_encode_tiff_async)
+  uph::TiffEncContext* tiffenc = nullptr;
+  int tiff_pages = 0;
 };
 
 namespace uph {

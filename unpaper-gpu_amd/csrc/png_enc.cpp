@@ -83,7 +83,8 @@ int sorted_order(const uint32_t* freq, int n, uint16_t* order) {
 
 void encode_stream_host(const uint8_t* px, int64_t stride, int32_t offset, const Shape& s, std::vector<uint8_t>* out) {
   // the filtered stream
-  std::vector<uint8_t> filt((size_t)s.total);
+  std::vector<uint8_t> rows((size_t)s.total);
+  uint8_t* filt = rows.data();
   const int off = offset & 7;
   for (int32_t y = 0; y < s.height; y++) {
     const HostRow cur{px + (int64_t)y * stride + (offset >> 3)};
@@ -91,10 +92,14 @@ void encode_stream_host(const uint8_t* px, int64_t stride, int32_t offset, const
     uint32_t sum[3] = {0, 0, 0};
     if (s.depth == 8) filter_sums(cur, off, up, off, y > 0, s, 0, 1, sum);
     const int f = choose_filter(s, sum);
-    uint8_t* dst = filt.data() + (int64_t)y * s.line;
+    uint8_t* dst = filt + (int64_t)y * s.line;
     dst[0] = (uint8_t)f;
     filter_row(cur, off, up, off, y > 0, s, f, 0, 1, dst);
   }
+  deflate_host(filt, s, out);
+}
+
+void deflate_host(const uint8_t* filt, const Shape& s, std::vector<uint8_t>* out) {
   // counts and the checksum
   PageTab t;
   memset(&t, 0, sizeof(t));
@@ -103,9 +108,9 @@ void encode_stream_host(const uint8_t* px, int64_t stride, int32_t offset, const
   HistVisitor hv{t.freq};
   for (int64_t g = 0; g < nseg; g++) {
     const int64_t lo = g * kSegBytes, hi = std::min<int64_t>(lo + kSegBytes, s.total);
-    parse_segment(filt.data(), lo, hi, s, hv);
+    parse_segment(filt, lo, hi, s, hv);
     uint32_t a, b;
-    adler_segment(filt.data() + lo, (int)(hi - lo), &a, &b);
+    adler_segment(filt + lo, (int)(hi - lo), &a, &b);
     adler_append(&A, &B, (uint64_t)(hi - lo), a, b);
   }
   t.adler = B << 16 | A;
@@ -121,7 +126,7 @@ void encode_stream_host(const uint8_t* px, int64_t stride, int32_t offset, const
   for (int64_t g = 0; g < nseg; g++) {
     CountSink cs;
     CodeTokens<CountSink> v(t.code, cs);
-    parse_segment(filt.data(), g * kSegBytes, std::min<int64_t>((g + 1) * kSegBytes, s.total), s, v);
+    parse_segment(filt, g * kSegBytes, std::min<int64_t>((g + 1) * kSegBytes, s.total), s, v);
     t.token_bits += cs.bits;
   }
   decide_size(&t, s.total);
@@ -133,7 +138,7 @@ void encode_stream_host(const uint8_t* px, int64_t stride, int32_t offset, const
     z[1] = 0x01;
     for (int64_t i = 0; i < s.total; i += kStoredBlock) {
       stored_header(i, s.total, z + stored_place(i) - 5);
-      memcpy(z + stored_place(i), filt.data() + i, (size_t)std::min<int64_t>(kStoredBlock, s.total - i));
+      memcpy(z + stored_place(i), filt + i, (size_t)std::min<int64_t>(kStoredBlock, s.total - i));
     }
     for (int k = 0; k < 4; k++) z[t.size - 4 + k] = (uint8_t)(t.adler >> (24 - 8 * k));
   } else {
@@ -143,7 +148,7 @@ void encode_stream_host(const uint8_t* px, int64_t stride, int32_t offset, const
     put_block_header(t, sink);
     CodeTokens<HostSink> v(t.code, sink);
     for (int64_t g = 0; g < nseg; g++)
-      parse_segment(filt.data(), g * kSegBytes, std::min<int64_t>((g + 1) * kSegBytes, s.total), s, v);
+      parse_segment(filt, g * kSegBytes, std::min<int64_t>((g + 1) * kSegBytes, s.total), s, v);
     sink.put(t.code[kEob] & 0xFFFFu, (int)(t.code[kEob] >> 16));
     sink.put(0, (8 - sink.n % 8) % 8);
     for (int k = 0; k < 4; k++) sink.put((t.adler >> (24 - 8 * k)) & 0xFFu, 8);

@@ -34,6 +34,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <vector>
+
 #include "buffer.h"
 #include "png_enc_core.h"
 
@@ -60,6 +62,9 @@ struct PngLaunch {
   uint32_t lds_bytes;
 };
 bool png_plan(const pngenc::Shape& s, PngLaunch* l);
+// k_png_table over tabs[0..n): a wave per table, whatever its stream is (the
+// TIFF encoder's strips take it too).
+void png_table_launch(pngenc::PageTab* tabs, unsigned n, hipStream_t st);
 
 // The device buffers of an encoder, allocated by the first encode and grown
 // on demand (the stream is waited for only then).
@@ -87,6 +92,9 @@ namespace pngenc {
 // png_enc.cpp
 bool check_image(const char* who, const void* src, int64_t stride, int32_t offset, int32_t width, int32_t height,
                  int32_t format, int32_t dpi, Shape* s);
+// The zlib stream of the s.total filtered bytes at `filt` (the core's LZ77
+// and entropy coding on the host; of `s` the parse reads bpp, line and total).
+void deflate_host(const uint8_t* filt, const Shape& s, std::vector<uint8_t>* out);
 }  // namespace pngenc
 
 }  // namespace uph

@@ -408,7 +408,7 @@ struct SlotLoop {
       ok = upload_staging(r, sl, npages) && jpeg_submit(sl, npages) && tiff_submit(sl, npages) &&
            uphip_batch_run(sl->b, sl->count) == 0;
     }
-    const PackedCodec* pc = packed_codec(sink);
+    const PackedCodec* pc = packed_codec(sink, r->out_fmt);
     if (!ok || (pc && pc->encode(sl->b, sink) != 0)) return fail_chunk(k, "run failed");
     phase[k] = RUNNING;
     state[k] = RUNNING;
@@ -447,7 +447,7 @@ struct SlotLoop {
     for (int s = 0; s < sl->count; s++) clean &= !sl->failed[(size_t)s];
     sl->direct_out = run.dsnk && clean;
     bool queued;
-    if (const PackedCodec* pc = packed_codec(sink)) {
+    if (const PackedCodec* pc = packed_codec(sink, r->out_fmt)) {
       // only the encoded files come back: sizes (already on the host), then
       // one copy of the packed files
       const int npg = sl->count * r->oc;

@@ -22,6 +22,7 @@
 #include "pdf.h"
 #include "runtime.h"
 #include "tiff_dec.h"
+#include "tiff_write.h"
 
 namespace uph {
 
@@ -84,7 +85,11 @@ struct UphipSink {
   //         page, at pdf_dpi; uphip_sink_pdf_bilevel)
   //   Png   lossless zlib streams of sheets of any format (uphip_sink_png: a PNG per
   //         page, pHYs from png_dpi; uphip_sink_pdf_lossless)
-  enum class Codec { Raw, Jpeg, Jp2, G4, Png };
+  //   Tiff  TIFF pages in the runner's output format (uphip_sink_tiff: a file per
+  //         page; uphip_sink_tiff_multipage: one file): Group 4 streams of
+  //         MONOWHITE sheets, Deflate strips of GRAY8 and RGB24 sheets; the
+  //         codec follows the format (packed_codec), resolution pdf_dpi
+  enum class Codec { Raw, Jpeg, Jp2, G4, Png, Tiff };
   Codec codec = Codec::Raw;
   UphipStoreFn store = nullptr;
   void* user = nullptr;
@@ -97,6 +102,8 @@ struct UphipSink {
   // one PDF of all the output pages (uphip_sink_pdf*): the encoded pages go to
   // the writer instead of files
   std::unique_ptr<uph::pdf::Writer> pdfw;
+  // one TIFF of all the output pages (uphip_sink_tiff_multipage)
+  std::unique_ptr<uph::tiff::Writer> tiffw;
   int32_t pdf_dpi = 300;
   uph::HostRegistration reg;
 };
@@ -242,7 +249,9 @@ struct PackedCodec {
   // packed download, or -- a page of size -1 -- encoded again on its own
   bool (*store_page)(UphipRunner* r, const UphipSink* k, int device, const Slot* sl, int s, int j);
 };
-const PackedCodec* packed_codec(const UphipSink* k);  // null for Raw and Jp2
+// null for Raw and Jp2; a Tiff sink's codec follows the runner's output
+// format: Group 4 for MONOWHITE sheets, Deflate strips otherwise
+const PackedCodec* packed_codec(const UphipSink* k, int32_t out_fmt);
 
 // runner_io.cpp
 void store_chunk_sheet(UphipRunner* r, const UphipSink* k, int device, const Slot* sl, int s, bool* ok);

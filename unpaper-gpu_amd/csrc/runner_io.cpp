@@ -51,52 +51,10 @@ bool output_pattern(const char* p, std::string* out) {
   return true;
 }
 
-// A Group 4 stream of a w x h page as a classic little-endian TIFF: header,
-// one IFD, the two resolution rationals, then the stream as the only strip.
+// A Group 4 stream of a w x h page as a TIFF file of its own (tiff::g4_file).
 bool write_tiff_g4(const std::string& path, const uint8_t* p, size_t n, int32_t w, int32_t h, int32_t dpi) {
-  constexpr int kEntries = 14;
-  constexpr uint32_t kIfd = 8, kRes = kIfd + 2 + kEntries * 12 + 4, kStrip = kRes + 16;
-  if (n > 0xFFFFFFFFu - kStrip) return fail("tiff_g4: a %zu-byte strip does not fit a classic TIFF", n);
   std::vector<uint8_t> f;
-  f.reserve(kStrip + n);
-  auto u16 = [&f](uint32_t v) {
-    f.push_back((uint8_t)v);
-    f.push_back((uint8_t)(v >> 8));
-  };
-  auto u32 = [&](uint32_t v) {
-    u16(v & 0xFFFF);
-    u16(v >> 16);
-  };
-  auto entry = [&](uint32_t tag, uint32_t type, uint32_t value) {  // type 3 SHORT, 4 LONG, 5 RATIONAL (offset)
-    u16(tag);
-    u16(type);
-    u32(1);
-    u32(value);  // a SHORT sits in the low half, the rest zero
-  };
-  u16(0x4949);
-  u16(42);
-  u32(kIfd);
-  u16(kEntries);
-  entry(256, 4, (uint32_t)w);        // ImageWidth
-  entry(257, 4, (uint32_t)h);        // ImageLength
-  entry(258, 3, 1);                  // BitsPerSample
-  entry(259, 3, 4);                  // Compression: CCITT T.6
-  entry(262, 3, 0);                  // PhotometricInterpretation: 0 is white
-  entry(266, 3, 1);                  // FillOrder: MSB first
-  entry(273, 4, kStrip);             // StripOffsets
-  entry(277, 3, 1);                  // SamplesPerPixel
-  entry(278, 4, (uint32_t)h);        // RowsPerStrip: one strip
-  entry(279, 4, (uint32_t)n);        // StripByteCounts
-  entry(282, 5, kRes);               // XResolution
-  entry(283, 5, kRes + 8);           // YResolution
-  entry(293, 4, 0);                  // T6Options
-  entry(296, 3, 2);                  // ResolutionUnit: inch
-  u32(0);                            // no further IFD
-  for (int i = 0; i < 2; i++) {
-    u32((uint32_t)dpi);
-    u32(1);
-  }
-  f.insert(f.end(), p, p + n);
+  if (!tiff::g4_file(p, n, w, h, dpi, &f)) return false;
   FILE* o = fopen(path.c_str(), "wb");
   if (!o) return fail("tiff_g4: cannot create %s", path.c_str());
   const bool ok = fwrite(f.data(), 1, f.size(), o) == f.size();
@@ -295,6 +253,26 @@ UphipSink* uphip_sink_png(const char* pattern, int64_t wrap, int32_t dpi) {
   return k;
 }
 
+UphipSink* uphip_sink_tiff(const char* pattern, int64_t wrap, int32_t dpi) {
+  if (!pattern) return fail("sink_tiff: null pattern"), nullptr;
+  if (!dpi_ok("sink_tiff", dpi)) return nullptr;
+  UphipSink* k = file_sink("sink_tiff", pattern, wrap, UphipSink::Codec::Tiff);
+  if (k) k->pdf_dpi = dpi ? dpi : 300;
+  return k;
+}
+
+UphipSink* uphip_sink_tiff_multipage(const char* path, int32_t dpi) {
+  if (!path) return fail("sink_tiff_multipage: null path"), nullptr;
+  if (!dpi_ok("sink_tiff_multipage", dpi)) return nullptr;
+  std::unique_ptr<tiff::Writer> w(new tiff::Writer());
+  if (!w->create(path, dpi)) return nullptr;
+  UphipSink* k = new UphipSink();
+  k->tiffw = std::move(w);
+  k->pdf_dpi = dpi ? dpi : 300;
+  k->codec = UphipSink::Codec::Tiff;
+  return k;
+}
+
 UphipSink* uphip_sink_pdf_lossless(const char* path, const UphipPdfMetadata* meta, int32_t dpi) {
   if (!path) return fail("sink_pdf_lossless: null path"), nullptr;
   if (!dpi_ok("sink_pdf_lossless", dpi)) return nullptr;
@@ -311,6 +289,11 @@ int uphip_tiff_g4_write(const char* path, const uint8_t* data, size_t len, int32
 
 int uphip_sink_finish(UphipSink* k) {
   if (!k) return fail("sink_finish: null sink"), -1;
+  if (k->tiffw) {
+    const bool ok = k->tiffw->finish();
+    k->tiffw.reset();
+    return ok ? 0 : -1;
+  }
   if (!k->pdfw) return 0;
   const bool ok = k->pdfw->close();
   k->pdfw.reset();
@@ -456,6 +439,18 @@ bool store_png_page(UphipRunner* r, const UphipSink* k, int, const Slot* sl, int
          write_file(sink_path(k, p.idx), file.data(), file.size());
 }
 
+// A Deflate TIFF page: its packed page into the sink's file of many pages or
+// a file of its own.
+bool store_tiff_page(UphipRunner* r, const UphipSink* k, int, const Slot* sl, int s, int j) {
+  const PackedPage p(r, sl, s, j);
+  const int32_t pw = r->out_w / r->oc;
+  if (p.size <= 0) return false;
+  if (k->tiffw) return k->tiffw->add_page_deflate(p.idx, p.data, (size_t)p.size, pw, r->out_h, r->out_fmt, k->pdf_dpi);
+  std::vector<uint8_t> file;
+  return tiff::deflate_file(p.data, (size_t)p.size, pw, r->out_h, r->out_fmt, k->pdf_dpi, &file) &&
+         write_file(sink_path(k, p.idx), file.data(), file.size());
+}
+
 constexpr PackedCodec kJpegCodec = {
     [](UphipBatch* b, const UphipSink* k) { return uphip_batch_encode_jpeg_async(b, k->quality, k->sampling); },
     uphip_batch_jpeg_sizes, uphip_batch_jpeg_download_async, store_jpeg_page};
@@ -463,6 +458,8 @@ constexpr PackedCodec kG4Codec = {[](UphipBatch* b, const UphipSink*) { return u
                                   uphip_batch_g4_sizes, uphip_batch_g4_download_async, store_g4_page};
 constexpr PackedCodec kPngCodec = {[](UphipBatch* b, const UphipSink*) { return uphip_batch_encode_png_async(b); },
                                    uphip_batch_png_sizes, uphip_batch_png_download_async, store_png_page};
+constexpr PackedCodec kTiffCodec = {[](UphipBatch* b, const UphipSink*) { return uphip_batch_encode_tiff_async(b); },
+                                    uphip_batch_tiff_sizes, uphip_batch_tiff_download_async, store_tiff_page};
 
 // The pages of sheet s of a slot's chunk as JPEG 2000 files: each page's
 // packed codewords from the device, its packets and boxes here.
@@ -501,8 +498,9 @@ void store_jp2_chunk_sheet(UphipRunner* r, const UphipSink* k, int device, const
 
 namespace uph {
 
-const PackedCodec* packed_codec(const UphipSink* k) {
+const PackedCodec* packed_codec(const UphipSink* k, int32_t out_fmt) {
   switch (k->codec) {
+    case UphipSink::Codec::Tiff: return out_fmt == UPHIP_FMT_MONOWHITE ? &kG4Codec : &kTiffCodec;
     case UphipSink::Codec::Jpeg: return &kJpegCodec;
     case UphipSink::Codec::G4: return &kG4Codec;
     case UphipSink::Codec::Png: return &kPngCodec;
@@ -515,7 +513,9 @@ const PackedCodec* packed_codec(const UphipSink* k) {
 // pdf_page_accumulator.c:44-62; here straight from the store task, the
 // writer orders the page tree).
 bool sink_write(const UphipSink* k, int64_t idx, const uint8_t* p, size_t n, int32_t w, int32_t h) {
-  if (k->codec == UphipSink::Codec::G4)  // a Group 4 stream has no header: the caller gives the page's size
+  if (k->tiffw) return k->tiffw->add_page_g4(idx, p, n, w, h, k->pdf_dpi);  // a Tiff sink's bilevel pages
+  if (k->codec == UphipSink::Codec::G4 || k->codec == UphipSink::Codec::Tiff)
+    // a Group 4 stream has no header: the caller gives the page's size
     return k->pdfw ? k->pdfw->add_page(idx, pdf::kCcitt, p, n, w, h, 0, 0, k->pdf_dpi)
                    : write_tiff_g4(sink_path(k, idx), p, n, w, h, k->pdf_dpi);
   if (!k->pdfw) return write_file(sink_path(k, idx), p, n);
@@ -527,7 +527,7 @@ bool sink_write(const UphipSink* k, int64_t idx, const uint8_t* p, size_t n, int
 
 // Sheet s of a slot's finished chunk into the sink, through the sink's codec.
 void store_chunk_sheet(UphipRunner* r, const UphipSink* k, int device, const Slot* sl, int s, bool* ok) {
-  if (const PackedCodec* c = packed_codec(k)) {
+  if (const PackedCodec* c = packed_codec(k, r->out_fmt)) {
     for (int j = 0; j < r->oc; j++)
       if (!c->store_page(r, k, device, sl, s, j)) *ok = false;
   } else if (k->codec == UphipSink::Codec::Jp2) {

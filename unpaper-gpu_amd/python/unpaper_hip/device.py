@@ -75,6 +75,11 @@ EXPORTED = [
     "uphip_tiff_probe", "uphip_tiff_read", "uphip_tiff_open", "uphip_tiff_close",
     "uphip_tiff_page_count", "uphip_tiff_page_probe", "uphip_tiff_read_page",
     "uphip_tiff_page_on_device", "uphip_tiff_decode", "uphip_source_tiff",
+    "uphip_tiff_encode_host", "uphip_tiff_encode", "uphip_tiff_encode_pages",
+    "uphip_tiff_writer_open", "uphip_tiff_writer_add_page_deflate", "uphip_tiff_writer_add_page_g4",
+    "uphip_tiff_writer_finish", "uphip_tiff_writer_close", "uphip_batch_encode_tiff_async",
+    "uphip_batch_tiff_sizes", "uphip_batch_tiff_download_async", "uphip_sink_tiff",
+    "uphip_sink_tiff_multipage",
 ]
 
 
@@ -310,6 +315,25 @@ def load_library(path=LIB_PATH):
         "uphip_tiff_decode": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p, C.c_int64,
                                         C.POINTER(A.PnmInfo)]),
         "uphip_source_tiff": (C.c_void_p, [C.c_char_p, C.c_int32]),
+        "uphip_tiff_encode_host": (C.c_int64, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                               C.c_int32, C.c_int32, C.c_void_p, C.c_int64]),
+        "uphip_tiff_encode": (C.c_int64, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                          C.c_int32, C.c_int32, C.c_void_p, C.c_int64]),
+        "uphip_tiff_encode_pages": (C.c_int64, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32,
+                                                C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64),
+                                                C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]),
+        "uphip_tiff_writer_open": (C.c_void_p, [C.c_char_p, C.c_int32]),
+        "uphip_tiff_writer_add_page_deflate": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t,
+                                                         C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+        "uphip_tiff_writer_add_page_g4": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t,
+                                                    C.c_int32, C.c_int32, C.c_int32]),
+        "uphip_tiff_writer_finish": (C.c_int, [C.c_void_p]),
+        "uphip_tiff_writer_close": (None, [C.c_void_p]),
+        "uphip_batch_encode_tiff_async": (C.c_int, [C.c_void_p]),
+        "uphip_batch_tiff_sizes": (C.c_int64, [C.c_void_p, C.POINTER(C.c_int64), C.c_int32]),
+        "uphip_batch_tiff_download_async": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
+        "uphip_sink_tiff": (C.c_void_p, [C.c_char_p, C.c_int64, C.c_int32]),
+        "uphip_sink_tiff_multipage": (C.c_void_p, [C.c_char_p, C.c_int32]),
     }
     for name, (res, args) in sig.items():
         if not hasattr(L, name):

@@ -199,6 +199,35 @@ class Batch:
             off += sizes[i]
         return out
 
+    def encode_tiff(self):
+        """Queue the TIFF output branch on the last run's pages: each page's
+        Deflate strips (uphip_batch_encode_tiff_async; GRAY8 and RGB24
+        output)."""
+        if self.lib.uphip_batch_encode_tiff_async(self.handle) != 0:
+            _check(self.lib)
+            raise UnpaperHipError("batch_encode_tiff failed")
+
+    def tiff_pages(self, pages):
+        """The packed pages of the last encode_tiff, one per output page
+        (TiffWriter.add_page_deflate takes each)."""
+        L = self.lib
+        self.wait()
+        sizes = (C.c_int64 * pages)()
+        total = L.uphip_batch_tiff_sizes(self.handle, sizes, pages)
+        _check(L)
+        if total <= 0:
+            raise UnpaperHipError("batch_tiff_sizes failed")
+        buf = np.zeros(total, np.uint8)
+        if L.uphip_batch_tiff_download_async(self.handle, buf.ctypes.data, total) != 0:
+            _check(L)
+            raise UnpaperHipError("batch_tiff_download failed")
+        self.wait()
+        out, off = [], 0
+        for i in range(pages):
+            out.append(buf[off:off + sizes[i]].tobytes())
+            off += sizes[i]
+        return out
+
     def output_ptr(self, sheet):
         """(device pointer, pitch) of output sheet `sheet` (waits for the run)."""
         pitch = C.c_int64()
@@ -615,6 +644,107 @@ def sink_pdf_lossless(path, meta=None, dpi=0):
     if not h:
         raise UnpaperHipError("sink_pdf_lossless failed")
     return _PdfSink(h, L.uphip_sink_destroy, (m, keep))
+
+
+def sink_tiff(pattern, wrap=0, dpi=0):
+    """One TIFF per output page, coded on the device (uphip_sink_tiff): Group
+    4 for MONOWHITE output, Deflate strips for GRAY8 and RGB24; dpi 0 = 300."""
+    L = load_library()
+    h = L.uphip_sink_tiff(pattern.encode(), wrap, dpi)
+    _check(L)
+    if not h:
+        raise UnpaperHipError("sink_tiff failed")
+    return _Handle(h, L.uphip_sink_destroy)
+
+
+def sink_tiff_multipage(path, dpi=0):
+    """All output pages into one TIFF (uphip_sink_tiff_multipage; codec as
+    sink_tiff).  Call finish() after the run."""
+    L = load_library()
+    h = L.uphip_sink_tiff_multipage(path.encode(), dpi)
+    _check(L)
+    if not h:
+        raise UnpaperHipError("sink_tiff_multipage failed")
+    return _PdfSink(h, L.uphip_sink_destroy)
+
+
+def tiff_encode(device_ptr, pitch, width, height, fmt, offset=0, dpi=0):
+    """uphip_tiff_encode: rows in device memory -> a one-page TIFF file
+    (Deflate strips; Group 4 for MONOWHITE, whose `offset` is the bit of a
+    row that holds pixel 0)."""
+    return _png(load_library().uphip_tiff_encode, device_ptr, pitch, offset, width, height, fmt, dpi)
+
+
+def tiff_encode_host(rows, width, fmt, offset=0, dpi=0):
+    """uphip_tiff_encode_host: a 2-D uint8 array of rows (no device); the
+    same bytes as tiff_encode."""
+    rows = np.ascontiguousarray(rows, np.uint8)
+    return _png(load_library().uphip_tiff_encode_host, rows.ctypes.data, rows.shape[1], offset, width,
+                rows.shape[0], fmt, dpi)
+
+
+def tiff_encode_pages(device_ptr, pitch, page_stride, npages, width, height, fmt, fold=0, device_out=None,
+                      device_capacity=0):
+    """uphip_tiff_encode_pages: byte-format pages in device memory -> their
+    packed pages (StripByteCounts, then the strips), a list of bytes;
+    device_out: device memory the encoder packs them into."""
+    L = load_library()
+    sizes = (C.c_int64 * npages)()
+    n = L.uphip_tiff_encode_pages(device_ptr, pitch, page_stride, npages, width, height, fmt, fold, sizes,
+                                  None, 0, device_out, device_capacity)
+    _check(L)
+    if n <= 0:
+        raise UnpaperHipError("tiff_encode_pages failed")
+    buf = np.zeros(n, np.uint8)
+    if L.uphip_tiff_encode_pages(device_ptr, pitch, page_stride, npages, width, height, fmt, fold, sizes,
+                                 buf.ctypes.data, n, device_out, device_capacity) != n:
+        _check(L)
+        raise UnpaperHipError("tiff_encode_pages failed")
+    out, off = [], 0
+    for i in range(npages):
+        out.append(buf[off:off + sizes[i]].tobytes())
+        off += sizes[i]
+    return out
+
+
+class TiffWriter:
+    """uphip_tiff_writer_*: one TIFF of many pages.  add_page_* take the
+    page's place in the file as `index` (-1: after the highest so far)."""
+
+    def __init__(self, path, dpi=0):
+        self.lib = load_library()
+        self.handle = self.lib.uphip_tiff_writer_open(path.encode(), dpi)
+        _check(self.lib)
+        if not self.handle:
+            raise UnpaperHipError("tiff_writer_open failed")
+
+    def add_page_deflate(self, page: bytes, width, height, fmt, index=-1, dpi=0):
+        if self.lib.uphip_tiff_writer_add_page_deflate(self.handle, index, page, len(page), width, height,
+                                                       fmt, dpi) != 0:
+            _check(self.lib)
+            raise UnpaperHipError("tiff_writer_add_page_deflate failed")
+
+    def add_page_g4(self, stream: bytes, width, height, index=-1, dpi=0):
+        if self.lib.uphip_tiff_writer_add_page_g4(self.handle, index, stream, len(stream), width, height,
+                                                  dpi) != 0:
+            _check(self.lib)
+            raise UnpaperHipError("tiff_writer_add_page_g4 failed")
+
+    def finish(self):
+        if self.lib.uphip_tiff_writer_finish(self.handle) != 0:
+            _check(self.lib)
+            raise UnpaperHipError("tiff_writer_finish failed")
+
+    def close(self):
+        if self.handle:
+            self.lib.uphip_tiff_writer_close(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def _png(fn, ptr, pitch, offset, width, height, fmt, dpi):
