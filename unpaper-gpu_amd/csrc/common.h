@@ -256,7 +256,9 @@ __device__ __forceinline__ uint8_t* sheet_plane(const Planes& P, int s, int k) {
 //                     measures each kernel's marginal cost (1 rotation band,
 //                     2 rotate, 4 mask move, 8 decode copy, 16 rotation points,
 //                     32 gray cells, 64 blur counts, 128 rotation final + line
-//                     walk; 256/512/1024/2048 rotate variants)
+//                     walk; 256/512/1024/2048 rotate variants; 65536 the
+//                     bicubic rotate's phase clocks of wave 0, 524288 the
+//                     row-loop clocks of every wave: kernels_rotate.hip)
 //   UPHIP_DIAG_NOISE  noise classify early exit (1, 2, 3)
 // Any of these gives wrong pages by design.
 #ifdef UPHIP_DIAG

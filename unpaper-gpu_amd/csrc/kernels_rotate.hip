@@ -567,14 +567,18 @@ __global__ void __launch_bounds__(kThreads) k_rotate_cubic_g8(PlaneRef src, Plan
 //     boundary meets at most two-way bank conflicts);
 //   * all-white stretches of a tile row (the page background) are detected
 //     from per-row non-white masks built while staging and skip the math;
+//   * a tile's rows are dealt to its eight waves round-robin (wave w: tile
+//     rows w, w + 8, ..., w + 40; rot_wave_row, rot_tiles.h), so that a band of
+//     text, a run of non-white rows, costs every wave about the same and no
+//     wave idles at the tile's last barrier for the others;
 //   * each wave buffers its six output rows in LDS and stores them 8 bytes
 //     per lane at the end (no global load after a store).
 // Every rounding operation of cubic_scale (interpolate.c:24-31) stays a
 // separate multiply or add in the reference's order, as in cubic2.
 // ---------------------------------------------------------------------------
 // kRFW x kRFH output tiles, kRFS floats a staged row: rot_tiles.h
-constexpr int kRFT = 512;   // threads per tile: 8 waves, kRFH / 8 consecutive rows each
-constexpr int kRFWaves = kRFT / 64;
+constexpr int kRFT = 512;   // threads per tile: 8 waves, kRFH / 8 rows each (rot_wave_row)
+static_assert(kRFWaves == kRFT / 64 && kRFH % kRFWaves == 0, "rot_wave_row deals kRFH rows to kRFT / 64 waves");
 
 // The 16 taps of pixels A and B as row pairs: t[p][j] = {tap row 2q, tap row
 // 2q+1} of column j for p = 2*pixel + q.  a[p] is the LDS byte address of
@@ -668,6 +672,11 @@ __device__ unsigned long long g_rot_phase[1024 * 8];
     atomicAdd(&g_rot_phase[8 * (blockIdx.x & 1023) + (k)], tn - tprev);      \
     tprev = tn;                                                              \
   }
+// (UPHIP_DIAG_DOUBLE bit 524288) the row loop's clocks of every wave of an
+// in-mask tile, by tile record: the sum over the tile's waves and the slowest
+// wave (how evenly rot_wave_row deals the non-white rows)
+constexpr int kRotWaveSlots = 1 << 18;
+__device__ unsigned int g_rot_wsum[kRotWaveSlots], g_rot_wmax[kRotWaveSlots];
 #else
 #define UPH_ROT_T(k)
 #endif
@@ -740,7 +749,7 @@ __global__ void __launch_bounds__(kRFT, UPH_ROT_MINB) k_rotate_cubic_g8f(
     const uint32_t* __restrict__ nlarge, RotPlane P, int max_rows, int diag, uint32_t m_gxy,
     uint32_t m_gx, int loop_count, int tgx, int tgy, uint32_t* colsum, int64_t cs_stride) {
   // dynamic LDS: window [max_rows][kRFS] floats, nw[max_rows] u64, then one
-  // (kRFH / 8) x kRFW byte output buffer per wave
+  // (kRFH / 8) x kRFW byte output buffer per wave (its row k: the wave's k-th row)
   extern __shared__ __attribute__((aligned(16))) float winf[];
   // colsum (optional): the output's column sums over all rows, added into
   // colsum[s * cs_stride + x] (the next mask scan's, masks.c:54-209), so that
@@ -930,13 +939,15 @@ __global__ void __launch_bounds__(kRFT, UPH_ROT_MINB) k_rotate_cubic_g8f(
   const float cuL = (tx0 - a.mx0) - tcx, cuR = (tx0 + kRFW - 1 - a.mx0) - tcx;
   const float bsL = cuL * a.sinval, bsR = cuR * a.sinval;
   constexpr int kRows = kRFH / kRFWaves;            // rows per wave
-  const int32_t yw = ty0 + wu * kRows;              // the wave's rows: yw .. yw + kRows-1
+  // image row of the wave's k-th row (k < kRows), increasing in k; obuf row k
+  auto wrow = [&](int k) -> int32_t { return ty0 + rot_wave_row(wu, k); };
   // Outside the mask a pixel is copied unchanged (deskew.c:268-286).  Those
   // source bytes are read into the wave's output buffer first: on gfx9 a
   // wait for a load also waits for every earlier store, so no global load
   // may follow the first store.  Tiles wholly inside the mask skip this.
   // The wave's output rows move through obuf with one mapping for loads and
-  // stores: lane -> row k0 + lane/16, bytes 8*(lane%16), k0 = 0, 4.
+  // stores: lane -> the wave's row k0 + lane/16 (image row wrow of it), bytes
+  // 8*(lane%16), k0 = 0, 4: four 128-byte row segments an instruction.
   const int cb = 8 * (lane & 15);
   const int32_t xo = tx0 + cb;
   const bool partial = T.flags & ROT_T_PARTIAL;
@@ -947,7 +958,7 @@ __global__ void __launch_bounds__(kRFT, UPH_ROT_MINB) k_rotate_cubic_g8f(
     for (int h = 0; h < kQ; h++) {
       q[h] = 0;
       const int rr = 4 * h + (lane >> 4);
-      const int32_t y = imin(yw + rr, P.H - 1);
+      const int32_t y = imin(wrow(rr), P.H - 1);
       const int32_t x = imin(xo, (int32_t)P.pitch - 8);  // rows are 256-byte pitched
       if (rr < kRows) q[h] = gload<uint64_t>(sbase + row_off(y, P.pitch) + x);
     }
@@ -972,7 +983,7 @@ __global__ void __launch_bounds__(kRFT, UPH_ROT_MINB) k_rotate_cubic_g8f(
       const int k = g + (lane >> 3), j = lane & 7;
       bool hit = false;
       if (k < kRows) {
-        const float cv = (yw + k - a.my0) - tcy;
+        const float cv = (wrow(k) - a.my0) - tcy;
         const float VC = scy + cv * a.cosval;
         const int32_t yl = (int)(VC - bsL), yr = (int)(VC - bsR);
         const int32_t r0 = imax(imin(yl, yr) - 1 - by0, 0);
@@ -995,6 +1006,9 @@ __global__ void __launch_bounds__(kRFT, UPH_ROT_MINB) k_rotate_cubic_g8f(
   // so a pixel's first tap sits at wbase + 4 (iy kRFS + ix)
   const uint32_t wbase = lds0 - 4u * (uint32_t)((1 + by0) * kRFS + 1 + xa);
   UPH_ROT_T(3)
+#ifdef UPHIP_DIAG
+  const unsigned long long twave = wall_clock64();
+#endif
   // Full tiles (every pixel inside the mask and the image, the window staged
   // and starting inside the image) take a copy of the row loop without the
   // per-pixel mask tests and their exec-mask branches.
@@ -1003,7 +1017,7 @@ __global__ void __launch_bounds__(kRFT, UPH_ROT_MINB) k_rotate_cubic_g8f(
   constexpr bool FULL = decltype(full_tag)::value;
 #pragma unroll
   for (int k = 0; k < kRows; k++) {
-    const int32_t y = yw + k;
+    const int32_t y = wrow(k);
     const int32_t v = y - a.my0;
     const bool rowin = FULL || ((v >= 0) & (v < sh) & (y < P.H));
     const float cv = v - tcy;
@@ -1092,7 +1106,7 @@ __global__ void __launch_bounds__(kRFT, UPH_ROT_MINB) k_rotate_cubic_g8f(
     // of the unrolled loop above)
 #pragma unroll 1
     for (int k = 0; k < kRows; k++) {
-      const int32_t y = yw + k;
+      const int32_t y = wrow(k);
       const int32_t v = y - a.my0;
       const bool rowin = (v >= 0) & (v < sh) & (y < P.H);
       const float cv = v - tcy;
@@ -1101,6 +1115,13 @@ __global__ void __launch_bounds__(kRFT, UPH_ROT_MINB) k_rotate_cubic_g8f(
       if (rowin & colB) obuf[k * kRFW + 64 + lane] = interp_bicubic(S, axB + VS, VC - bsB).r;
     }
   }
+#ifdef UPHIP_DIAG
+  if (UPH_DIAG_BITS(diag, 524288) && lane == 0 && ti < kRotWaveSlots) {
+    const unsigned int dt = (unsigned int)(wall_clock64() - twave);
+    atomicAdd(&g_rot_wsum[ti], dt);
+    atomicMax(&g_rot_wmax[ti], dt);
+  }
+#endif
   UPH_ROT_T(4)
   // the wave's rows as 8-byte stores: lane -> row k0 + lane/16, bytes
   // 8*(lane%16).  One wave's LDS operations complete in order, so its reads
@@ -1113,13 +1134,13 @@ __global__ void __launch_bounds__(kRFT, UPH_ROT_MINB) k_rotate_cubic_g8f(
       const int rr = k0 + (lane >> 4);
       if (rr < kRows) {
         const uint64_t q = *reinterpret_cast<const uint64_t*>(obuf + rr * kRFW + cb);
-        gstore<uint64_t>(dbase + row_off(yw + rr, P.pitch) + xo, q);
+        gstore<uint64_t>(dbase + row_off(wrow(rr), P.pitch) + xo, q);
       }
     }
   } else
   for (int k0 = 0; k0 < kRows && !UPH_DIAG_BITS(diag, 8192); k0 += 4) {
     const int rr = k0 + (lane >> 4);
-    const int32_t y = yw + rr, x = xo;
+    const int32_t y = wrow(rr), x = xo;
     if (rr < kRows && y < P.H && x < P.W) {
       const uint64_t q = *reinterpret_cast<const uint64_t*>(obuf + rr * kRFW + cb);
       uint8_t* d = dbase + row_off(y, P.pitch) + x;
@@ -1137,7 +1158,7 @@ __global__ void __launch_bounds__(kRFT, UPH_ROT_MINB) k_rotate_cubic_g8f(
     if (!full) {
 #pragma unroll
       for (int k = 0; k < kRows; k++) {
-        if (yw + k >= P.H) break;
+        if (wrow(k) >= P.H) break;  // and so is every later row: wrow increases with k
         sA += obuf[k * kRFW + lane];
         sB += obuf[k * kRFW + 64 + lane];
       }
@@ -1220,11 +1241,25 @@ bool launch_rotate_mask(const PlaneRef& src, const PlaneRef& dst, const RotateAr
         src.P.pitch * (int64_t)src.P.H < (1ll << 31) && !(diag_double() & 256)) {
       const dim3 fgrid((src.P.W + kRFW - 1) / kRFW, (src.P.H + kRFH - 1) / kRFH, count);
       const uint32_t mgxy = div_magic(fgrid.x * fgrid.y), mgx = div_magic(fgrid.x);
-      const int dd = diag_double() & (512 | 1024 | 2048 | 8192 | 65536 | 131072);
+      const int dd = diag_double() & (512 | 1024 | 2048 | 8192 | 65536 | 131072 | 524288);
 #ifdef UPHIP_DIAG
       struct PhasePrint {  // after the launches below: the per-tile phase clocks
         hipStream_t st;
         ~PhasePrint() {
+          if (diag_double() & 524288) {  // every wave's row loop: the tile's mean wave and its slowest
+            static unsigned int ws[kRotWaveSlots], wm[kRotWaveSlots], wz[kRotWaveSlots];
+            hipStreamSynchronize(st);
+            hipMemcpyFromSymbol(ws, HIP_SYMBOL(g_rot_wsum), sizeof(ws));
+            hipMemcpyFromSymbol(wm, HIP_SYMBOL(g_rot_wmax), sizeof(wm));
+            hipMemcpyToSymbol(HIP_SYMBOL(g_rot_wsum), wz, sizeof(wz));
+            hipMemcpyToSymbol(HIP_SYMBOL(g_rot_wmax), wz, sizeof(wz));
+            unsigned long long n = 0, sum = 0, mx = 0;
+            for (int i = 0; i < kRotWaveSlots; i++)
+              if (wm[i]) n++, sum += ws[i], mx += wm[i];
+            if (n)
+              fprintf(stderr, "rotate row loop (10 ns ticks/tile, %llu tiles, %d waves a tile): mean wave %.1f "
+                      "slowest wave %.1f\n", n, kRFWaves, (double)sum / kRFWaves / n, (double)mx / n);
+          }
           if (!(diag_double() & 65536)) return;
           static unsigned long long hh[1024 * 8], z[1024 * 8];
           unsigned long long h[8] = {0, 0, 0, 0, 0, 0, 0, 0};

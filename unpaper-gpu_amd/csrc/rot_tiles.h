@@ -25,9 +25,28 @@
 
 enum {
   kRFW = 128, /* output columns per tile (2 per lane) */
-  kRFH = 48,  /* output rows per tile, 6 per wave (96-row tiles measured slower: DESIGN §5) */
-  kRFS = 144  /* staged row stride in floats (>= 141-float window rows at 5 deg) */
+  kRFH = 48,  /* output rows per tile, every 8th to one wave: 6 per wave (rot_wave_row;
+                 96-row tiles measured slower: DESIGN §5) */
+  kRFS = 144, /* staged row stride in floats (>= 141-float window rows at 5 deg) */
+  kRFWaves = 8 /* waves per tile */
 };
+
+/* Tile row (0 .. kRFH - 1) of the k-th row (k < kRFH / kRFWaves) of wave wu:
+ * the rows are dealt round-robin, wave wu takes wu, wu + 8, ..., wu + 40.
+ * Ink comes in horizontal bands, and the kernel skips the arithmetic of rows
+ * whose taps are all white: a band of n consecutive rows gives every wave at
+ * most ceil(n / 8) of them, where consecutive rows per wave gave some waves
+ * six and others none while the tile waits for its slowest wave.
+ * A bijection onto the tile's rows, strictly increasing in k: the kernel's
+ * "rows from here on are below the image" tests rely on that
+ * (tests/test_rot_rows_cpu.py). */
+ROT_FN int rot_wave_row(int wu, int k) {
+#if defined(UPHIP_DIAG) && defined(UPH_ROT_ROWS_CONSECUTIVE)
+  return wu * (kRFH / kRFWaves) + k; /* tuning build only: the assignment before, for the A/B */
+#else
+  return wu + kRFWaves * k;
+#endif
+}
 
 /* RotTile.flags */
 enum {
