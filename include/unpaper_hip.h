@@ -1131,6 +1131,25 @@ int uphip_memcpy_dtoh(void *dst, const void *src, size_t bytes);
  * `stride`-th float of |x| < 120 (sin/cos) and 2^-60 <= |x| < 2^61 (pow),
  * both signs.  counts = {sinf, cosf, powf mismatches, inputs}.  */
 int uphip_check_libm(uint32_t stride, uint64_t counts[4]);
+/* Which kernels ("arms") the launcher of a filter takes for an image of this
+ * format and size: the names, space separated, into out (cap bytes); returns
+ * their number, -1 for an unknown filter, invalid parameters or a short
+ * buffer.  Host only: no device is needed.
+ *   filter       params                          threshold
+ *   blackfilter  NULL                            -
+ *   noisefilter  NULL                            -
+ *   grayfilter   UphipGrayfilterParameters *     the image's abs_black_threshold
+ *   blurfilter   UphipBlurfilterParameters *     abs_white_threshold
+ *   axis         NULL                            -
+ * "axis": the column and the row sums under detect_masks, detect_border and
+ * the blackfilter's stripes.  fused != 0: as a stage of a batch whose GRAY8
+ * decode hands its bit-planes on to the filters (a plain GRAY8 page per
+ * sheet), 0: the single-image entry points above. */
+int32_t uphip_filter_arms(const char *filter, int32_t format, int32_t width,
+                          int32_t height, const void *params, uint8_t threshold,
+                          int32_t fused, char *out, size_t cap);
+/* Every arm name uphip_filter_arms can return, space separated. */
+const char *uphip_filter_arm_names(void);
 /* Pinned (page-locked) host memory, DMA-capable from every device. */
 void *uphip_host_alloc(size_t bytes);
 void uphip_host_free(void *ptr);

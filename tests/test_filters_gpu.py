@@ -3,50 +3,66 @@ peers): HIP == oracle bit for bit.  The small hand-made scenes restate the
 reference's own unit tests (tests/cuda_filters_test.c:42-383,
 tests/cuda_deskew_test.c:18-40); the synthetic pages exercise the default
 parameters, order-dependent cases (clustered specks, edge-zone quirks, wipe
-feedback on colour tiles, flood fills) and odd geometries."""
+feedback on colour tiles, flood fills) and odd geometries.
+
+The filter cases (pages, parameters, what each is for) live in
+tests/filter_cases.py; tests/test_filter_cases.py checks on the CPU that the
+oracle changes every page it is not declared a no-op on, and that a case made
+for one arm of a launcher (a kernel picked by sheet size or geometry) selects
+it.  What that test measured in the oracle for the arm cases:
+
+  case                         arms                                  oracle
+  blackfilter short-16M        black.resolve_short                   1 fill, 260 366 flood calls, depth 33,
+    4104 x 4096, 3 formats                                           124 639 px changed (GRAY8)
+  blackfilter stairs-spill     black.resolve_long, stack in HBM      depth 1205, 26 701 px
+  blackfilter stairs-control   black.resolve_long, stack in LDS      depth 605, 13 501 px
+  blackfilter stairs-spill-twice  two flights of 600 steps           depth 1220, 53 402 px
+  blackfilter stairs-16M       black.resolve_short, stack in HBM     depth 1205, 84 321 px
+  blackfilter two-fills        (2 fills a sheet)                     2 fills, 16 200 px
+  noisefilter 1024-lds         noise.group_1024, buckets_shifted     5 426 triggers, 8 513 px
+  noisefilter 1024-big           4000 x 4200                         198 297 triggers, 181 033 px
+  noisefilter 1024-allseq        intensity 6                         10 268 triggers, 8 469 px
+  noisefilter 256-tall-lds     noise.group_256, buckets_shifted      1 579 triggers, 2 035 px
+  noisefilter 256-tall-big       300 x 4200                          38 450 triggers, 20 367 px
+  grayfilter ch256             gray.cells_generic                    8 800 / 712 241 px (300x200 / 1001x777)
+  grayfilter w16400            gray.cells_generic                    708 260 px
+  grayfilter lds-edge-512/513  gray.tiles_lds / gray.tiles_generic   45 287 / 45 413 px (GRAY8)
+  blurfilter w65600            blur.counts_generic, resolve_generic_hbm  594 px
+  blurfilter rows200           blur.resolve_generic_hbm (23 115 rects)   11 991 px
+  blurfilter sh65536           blur.counts_generic                   declared no-op (no block fits)
+  masks / border 300 x 2100    axis.rowsum_stride (RGB24, Y400A)     masks y 25..2065, border (0, 10, 1, 61)
+  masks / border 1200 x 300    axis.rowsum_gray_wave                 masks (25, 25, 1170, 270), border (45, 0, 21, 1)
+
+blurfilter rows200 differed from the oracle when it was added (the HIP filter
+wiped nothing): k_blur_resolve staged every count in LDS, and past the CU's
+160 KiB its launch failed unseen.  It now reads the counts in HBM where they
+do not fit (blur.resolve_generic_hbm).
+"""
 import math
 
 import numpy as np
 import pytest
 
+import filter_cases as FC
+from filter_cases import both
 from unpaper_hip import ctypes_abi as A
 from unpaper_hip.hostimage import HostImage
-from helpers import FORMATS, assert_same, make_image
+from helpers import BYTE_FORMATS, FORMATS, make_image
 
 pytestmark = pytest.mark.gpu
 
-WHITE, BLACK = A.Pixel(255, 255, 255), A.Pixel(0, 0, 0)
 
-
-def blank(w, h, fmt, thr):
-    shape = {A.FMT_RGB24: (h, w, 3), A.FMT_Y400A: (h, w, 2)}.get(fmt, (h, w))
-    return HostImage.from_array(np.full(shape, 255, np.uint8), fmt, abs_black_threshold=thr)
-
-
-def put(oracle, h, x, y, px):
-    oracle.wipe_rectangle(h, A.rect(x, y, x, y), px)
-
-
-def both(hip, oracle, h, op_hip, op_oracle):
-    d = hip.upload(h)
-    op_hip(d)
-    op_oracle(h)
-    assert_same(d.to_host(), h)
+def ids(cases):
+    return [c.id for c in cases]
 
 
 # ---------------------------------------------------------------- noisefilter
-def scene_noise(oracle, h):          # cuda_filters_test.c:42-54
-    put(oracle, h, 5, 5, BLACK)
-    oracle.wipe_rectangle(h, A.rect(15, 10, 17, 12), BLACK)
+def scene_noise():          # cuda_filters_test.c:42-54
+    return "scene-"
 
 
-def scene_noise_diag(oracle, h):     # cuda_filters_test.c:56-75
-    for i in range(4):
-        put(oracle, h, 2 + i, 2 + i, BLACK)
-    for dx, dy in [(0, 0), (1, 0), (-1, 0), (0, 1), (0, -1)]:
-        put(oracle, h, 12 + dx, 12 + dy, BLACK)
-    put(oracle, h, 24, 6, BLACK)
-    put(oracle, h, 25, 6, BLACK)
+def scene_noise_diag():     # cuda_filters_test.c:56-75
+    return "scene-diag-"
 
 
 @pytest.mark.parametrize("scene,fmt,size,thr,intensity,white", [
@@ -56,316 +72,174 @@ def scene_noise_diag(oracle, h):     # cuda_filters_test.c:56-75
     (scene_noise, A.FMT_Y400A, (20, 16), 64, 3, 180),
 ])
 def test_noisefilter_reference_scenes(hip, oracle, scene, fmt, size, thr, intensity, white):
-    h = blank(*size, fmt, thr)
-    scene(oracle, h)
-    both(hip, oracle, h, lambda d: hip.noisefilter(d, intensity, white),
-         lambda o: oracle.noisefilter(o, intensity, white))
+    case, = [c for c in FC.noise_scene_cases() if c.name == scene() + str(intensity)]
+    h = case.page()
+    assert (case.fmt, case.args) == (fmt, (intensity, white))
+    assert (h.width, h.height, h.abs_black_threshold) == size + (thr,)
+    both(hip, oracle, case)
 
 
 def test_noisefilter_rgb_scene(hip, oracle):  # cuda_filters_test.c:77-90
-    h = blank(32, 24, A.FMT_RGB24, 64)
-    put(oracle, h, 4, 4, A.Pixel(30, 0, 0))
-    put(oracle, h, 5, 4, A.Pixel(28, 0, 0))
-    oracle.wipe_rectangle(h, A.rect(14, 10, 16, 12), A.Pixel(20, 40, 60))
-    both(hip, oracle, h, lambda d: hip.noisefilter(d, 2, 200),
-         lambda o: oracle.noisefilter(o, 2, 200))
+    both(hip, oracle, FC.noise_scene_cases()[-1])
 
 
 @pytest.mark.parametrize("fmt", FORMATS)
-@pytest.mark.parametrize("size,seed,specks", [((300, 200), 1, 400), ((640, 480), 2, 3000),
-                                              ((129, 257), 3, 800), ((1000, 700), 4, 6000)])
-@pytest.mark.parametrize("intensity", [4, 2, 6])
+@pytest.mark.parametrize("size,seed,specks", FC.NOISE_PAGE_SIZES)
+@pytest.mark.parametrize("intensity", FC.NOISE_INTENSITIES)
 def test_noisefilter_pages(hip, oracle, fmt, size, seed, specks, intensity):
-    # dense specks -> many clustered (sequentially resolved) components; specks
-    # touch the left/top edge -> the unsigned-loop quirk zone
-    h = make_image(*size, fmt, seed=seed, specks=specks, margin=0)
-    both(hip, oracle, h, lambda d: hip.noisefilter(d, intensity, 229),
-         lambda o: oracle.noisefilter(o, intensity, 229))
+    both(hip, oracle, FC.noise_page_case(fmt, size, seed, specks, intensity))
 
 
 @pytest.mark.parametrize("fmt", [A.FMT_GRAY8, A.FMT_RGB24])
-@pytest.mark.parametrize("density,intensity", [(0.12, 4), (0.3, 4), (0.3, 2), (0.55, 3)])
+@pytest.mark.parametrize("density,intensity", FC.NOISE_SALT)
 def test_noisefilter_dense_salt(hip, oracle, fmt, density, intensity):
-    # so many small components per 64x64 tile that the classify kernel's LDS
-    # work lists overflow and it takes its row-loop path
-    rng = np.random.default_rng(int(density * 100) + intensity)
-    g = np.where(rng.random((230, 301)) < density, rng.integers(0, 200, (230, 301)), 255)
-    g = g.astype(np.uint8)
-    if fmt == A.FMT_RGB24:
-        h = HostImage.from_array(np.repeat(g[:, :, None], 3, axis=2), fmt)
-    else:
-        h = HostImage.from_array(g, fmt)
-    both(hip, oracle, h, lambda d: hip.noisefilter(d, intensity, 229),
-         lambda o: oracle.noisefilter(o, intensity, 229))
+    both(hip, oracle, FC.noise_salt_case(fmt, density, intensity))
 
 
 def test_noisefilter_edge_quirk(hip, oracle):
-    # components hugging x < level / y < level-1, where the reference's ring
-    # loops skip whole rows (int32 vs uint32 comparison)
-    g = np.full((40, 50), 255, np.uint8)
-    for (x, y) in [(0, 0), (1, 0), (0, 5), (1, 6), (2, 10), (0, 20), (3, 1), (10, 0), (11, 1),
-                   (20, 2), (21, 2), (22, 2), (2, 30), (2, 31), (3, 31), (4, 31), (1, 32)]:
-        g[y, x] = 0
-    h = HostImage.from_array(g, A.FMT_GRAY8)
-    both(hip, oracle, h, lambda d: hip.noisefilter(d, 4, 229),
-         lambda o: oracle.noisefilter(o, 4, 229))
-
-
-def noisy_scan(w, h, page, specks, seed, quality=75, border=True, dashes=True):
-    """A synthetic page made to look like a poor scan: clustered 1-px specks
-    (sequentially resolved components), a ragged dark left border (the
-    edge zone; its interior is the no-op triggers k_noise_classify drops), a
-    dashed rule in the top zone (one row of several hundred triggers), all
-    through a JPEG round trip (compression noise)."""
-    import io
-    from PIL import Image
-    from unpaper_hip.pipeline import synth_page_host
-    g = synth_page_host(w, h, page).copy()
-    rng = np.random.default_rng(seed)
-    ys, xs = rng.integers(0, h, specks), rng.integers(0, w, specks)
-    g[ys, xs] = rng.integers(0, 120, specks)
-    if border:
-        edge = 20 + rng.integers(0, 12, h)
-        for y in range(h):
-            g[y, :edge[y]] = 30
-    if dashes:
-        g[3, 40::2] = 0
-        g[9, 100::3] = 10
-    b = io.BytesIO()
-    Image.fromarray(g).save(b, "JPEG", quality=quality)
-    return np.asarray(Image.open(io.BytesIO(b.getvalue()))).copy()
+    both(hip, oracle, FC.noise_edge_quirk_case())
 
 
 @pytest.mark.parametrize("fmt", [A.FMT_GRAY8, A.FMT_RGB24])
-@pytest.mark.parametrize("specks,intensity", [(40000, 4), (40000, 2), (6000, 4), (800, 3), (800, 4)])
+@pytest.mark.parametrize("specks,intensity", FC.NOISE_GROUP_CAPS)
 def test_noisefilter_group_caps(hip, oracle, fmt, specks, intensity):
-    # 40000 / 6000 specks: more than 4096 sequential triggers (k_noise_group's
-    # global layout); 800: within its LDS layout; all with rows of more than
-    # 256 triggers (the dashed rules: the block-wide bucket sort)
-    g = noisy_scan(1240, 1754, 3, specks, specks + intensity)
-    h = HostImage.from_array(np.repeat(g[:, :, None], 3, axis=2) if fmt == A.FMT_RGB24 else g, fmt)
-    both(hip, oracle, h, lambda d: hip.noisefilter(d, intensity, 229),
-         lambda o: oracle.noisefilter(o, intensity, 229))
+    both(hip, oracle, FC.noise_group_caps_case(fmt, specks, intensity))
 
 
-def test_noisefilter_border_quirk_strip(hip, oracle):
-    # a solid border band with thin spurs reaching into the quirk strip
-    # (x < 7, y < 6): the no-op trigger test must leave those in the sequence
-    g = np.full((300, 400), 255, np.uint8)
-    g[:, :25] = 0
-    g[:40, :] = 0
-    for y in range(45, 300, 7):
-        g[y, 25:25 + (y % 11)] = 0      # spurs off the band's edge
-        g[y + 1, 3] = 255               # notches inside the quirk strip
-    g[50:60, 0:2] = 255
-    g[2, 100:300:2] = 255
-    h = HostImage.from_array(g, A.FMT_GRAY8)
-    both(hip, oracle, h, lambda d: hip.noisefilter(d, 4, 229),
-         lambda o: oracle.noisefilter(o, 4, 229))
+@pytest.mark.parametrize("intensity", FC.NOISE_QUIRK_INTENSITIES)
+def test_noisefilter_border_quirk_strip(hip, oracle, intensity):
+    both(hip, oracle, FC.noise_quirk_strip_case(intensity))
+
+
+@pytest.mark.parametrize("fmt", [A.FMT_GRAY8, A.FMT_RGB24])
+@pytest.mark.parametrize("big", FC.NOISE_BIG, ids=[b[0] for b in FC.NOISE_BIG])
+def test_noisefilter_group_1024(hip, oracle, fmt, big):
+    both(hip, oracle, FC.noise_big_case(fmt, *big))
+
+
+@pytest.mark.parametrize("fmt", [A.FMT_GRAY8, A.FMT_RGB24])
+@pytest.mark.parametrize("tall", FC.NOISE_TALL, ids=[t[0] for t in FC.NOISE_TALL])
+def test_noisefilter_tall_buckets(hip, oracle, fmt, tall):
+    both(hip, oracle, FC.noise_tall_case(fmt, *tall))
 
 
 # ---------------------------------------------------------------- grayfilter
 def test_grayfilter_reference_scene(hip, oracle):  # cuda_filters_test.c:296-331
-    h = blank(8, 8, A.FMT_GRAY8, 50)
-    oracle.wipe_rectangle(h, A.rect(0, 0, 3, 3), A.Pixel(150, 150, 150))
-    oracle.wipe_rectangle(h, A.rect(4, 0, 7, 3), A.Pixel(80, 80, 80))
-    p = A.GrayfilterParameters(A.RectangleSize(4, 4), A.Delta(4, 4), 127)
-    both(hip, oracle, h, lambda d: hip.grayfilter(d, p), lambda o: oracle.grayfilter(o, p))
+    both(hip, oracle, FC.gray_scene_case())
 
 
 @pytest.mark.parametrize("fmt", FORMATS)
-@pytest.mark.parametrize("size", [(300, 200), (1001, 777), (50, 50), (7, 3)])
-@pytest.mark.parametrize("params", [((50, 50), (20, 20), 127), ((30, 20), (15, 8), 127),
-                                    ((50, 50), (20, 20), 200), ((13, 7), (5, 3), 60)])
+@pytest.mark.parametrize("size", FC.GRAY_SIZES)
+@pytest.mark.parametrize("params", FC.GRAY_PARAMS)
 def test_grayfilter_pages(hip, oracle, fmt, size, params):
-    h = make_image(*size, fmt, seed=5)
-    p = A.GrayfilterParameters(A.RectangleSize(*params[0]), A.Delta(*params[1]), params[2])
-    both(hip, oracle, h, lambda d: hip.grayfilter(d, p), lambda o: oracle.grayfilter(o, p))
+    both(hip, oracle, FC.gray_page_case(fmt, size, params))
 
 
-@pytest.mark.parametrize("black", [40, 100, 170])
+@pytest.mark.parametrize("black", FC.GRAY_FEEDBACK_BLACK)
 def test_grayfilter_feedback_rgb(hip, oracle, black):
-    # saturated colour blocks: gray > black threshold but min(rgb) tiny, so a
-    # tile fails on the original image and passes once earlier tiles are wiped
-    rng = np.random.default_rng(7)
-    rgb = np.full((260, 330, 3), 255, np.uint8)
-    for _ in range(60):
-        x, y = int(rng.integers(0, 320)), int(rng.integers(0, 250))
-        rgb[y:y + int(rng.integers(3, 30)), x:x + int(rng.integers(3, 30))] = \
-            [int(rng.integers(200, 256)), int(rng.integers(200, 256)), int(rng.integers(0, 30))]
-    h = HostImage.from_array(rgb, A.FMT_RGB24, abs_black_threshold=black)
-    for thr in (127, 160, 90):
-        p = A.GrayfilterParameters(A.RectangleSize(50, 50), A.Delta(20, 20), thr)
-        hh = h.copy()
-        both(hip, oracle, hh, lambda d: hip.grayfilter(d, p), lambda o: oracle.grayfilter(o, p))
+    for case in FC.gray_feedback_cases(black):
+        both(hip, oracle, case)
+
+
+@pytest.mark.parametrize("case", FC.gray_arm_cases(), ids=ids(FC.gray_arm_cases()))
+def test_grayfilter_arms(hip, oracle, case):
+    both(hip, oracle, case)
 
 
 # ---------------------------------------------------------------- blurfilter
 def test_blurfilter_reference_scene(hip, oracle):  # cuda_filters_test.c:337-383
-    h = blank(16, 16, A.FMT_GRAY8, 64)
-    for (x, y) in [(1, 5), (2, 5), (1, 6)]:
-        put(oracle, h, x, y, BLACK)
-    oracle.wipe_rectangle(h, A.rect(8, 4, 11, 7), BLACK)
-    p = A.BlurfilterParameters(A.RectangleSize(4, 4), A.Delta(2, 2), 0.1)
-    both(hip, oracle, h, lambda d: hip.blurfilter(d, p, 200),
-         lambda o: oracle.blurfilter(o, p, 200))
+    both(hip, oracle, FC.blur_scene_case())
 
 
 @pytest.mark.parametrize("fmt", FORMATS)
-@pytest.mark.parametrize("size", [(2480 // 4, 3508 // 4), (1001, 777), (99, 300), (100, 100)])
-@pytest.mark.parametrize("params", [((100, 100), (50, 50), 0.01), ((40, 30), (15, 20), 0.05),
-                                    ((64, 64), (64, 13), 0.2)])
+@pytest.mark.parametrize("size", FC.BLUR_SIZES)
+@pytest.mark.parametrize("params", FC.BLUR_PARAMS)
 def test_blurfilter_pages(hip, oracle, fmt, size, params):
-    h = make_image(*size, fmt, seed=6, specks=300)
-    p = A.BlurfilterParameters(A.RectangleSize(*params[0]), A.Delta(*params[1]), params[2])
-    both(hip, oracle, h, lambda d: hip.blurfilter(d, p, 229),
-         lambda o: oracle.blurfilter(o, p, 229))
+    both(hip, oracle, FC.blur_page_case(fmt, size, params))
+
+
+@pytest.mark.parametrize("fmt", FORMATS)
+@pytest.mark.parametrize("size", FC.BLUR_EXTRA_SIZES)
+@pytest.mark.parametrize("params", FC.BLUR_PARAMS)
+def test_blurfilter_pages_above_one_block(hip, oracle, fmt, size, params):
+    both(hip, oracle, FC.blur_page_case(fmt, size, params))
 
 
 @pytest.mark.parametrize("fmt", [A.FMT_GRAY8, A.FMT_RGB24])
-@pytest.mark.parametrize("width", [1320, 2000, 3960, 4480, 4520])
+@pytest.mark.parametrize("width", FC.BLUR_WIDE_WIDTHS)
 def test_blurfilter_wide_rows(hip, oracle, fmt, width):
-    # rows of 33 .. 112 blocks take the chunked scalar resolver (C4's 99),
-    # 113 the generic one
-    h = make_image(width, 300, fmt, seed=7, specks=600)
-    for params in (((40, 30), (15, 20), 0.05), ((40, 40), (40, 10), 0.3)):
-        p = A.BlurfilterParameters(A.RectangleSize(*params[0]), A.Delta(*params[1]), params[2])
-        both(hip, oracle, h.copy(), lambda d: hip.blurfilter(d, p, 229),
-             lambda o: oracle.blurfilter(o, p, 229))
+    for case in FC.blur_wide_cases(fmt, width):
+        both(hip, oracle, case)
+
+
+@pytest.mark.parametrize("case", FC.blur_arm_cases(), ids=ids(FC.blur_arm_cases()))
+def test_blurfilter_arms(hip, oracle, case):
+    both(hip, oracle, case)
 
 
 # ---------------------------------------------------------------- blackfilter
-def black_params(oracle, size=(20, 20), step=(5, 5), depth=(500, 500), thr=242, intensity=20,
-                 direction=(True, True), exclusions=()):
-    p = oracle.default_options().blackfilter_parameters
-    p.scan_size = A.RectangleSize(*size)
-    p.scan_step = A.Delta(*step)
-    p.scan_depth.horizontal, p.scan_depth.vertical = depth
-    p.abs_threshold = thr
-    p.intensity = intensity
-    p.scan_direction = A.Direction(*direction)
-    p.exclusions_count = len(exclusions)
-    for i, e in enumerate(exclusions):
-        p.exclusions[i] = A.rect(*e)
-    return p
-
-
 def test_blackfilter_reference_scene(hip, oracle):  # cuda_filters_test.c:249-290
-    h = blank(32, 24, A.FMT_GRAY8, 128)
-    oracle.wipe_rectangle(h, A.rect(8, 0, 11, 23), BLACK)
-    p = black_params(oracle, (4, 4), (2, 2), (32, 24), int(255 * np.float32(0.9)), 2)
-    both(hip, oracle, h, lambda d: hip.blackfilter(d, p), lambda o: oracle.blackfilter(o, p))
-
-
-def band_page(w, h, fmt, band, seed, noise=True):
-    rng = np.random.default_rng(seed)
-    g = make_image(w, h, A.FMT_GRAY8, seed=seed).to_gray()
-    x0, x1, y0, y1 = band
-    g[y0:y1, x0:x1] = rng.integers(0, 11, size=(y1 - y0, x1 - x0)) if noise else 0
-    if fmt == A.FMT_GRAY8:
-        return HostImage.from_array(g, fmt)
-    if fmt == A.FMT_RGB24:
-        return HostImage.from_array(np.repeat(g[:, :, None], 3, axis=2), fmt)
-    if fmt == A.FMT_Y400A:
-        return HostImage.from_array(np.stack([g, np.full_like(g, 255)], axis=2), fmt)
-    return HostImage.from_array(g >= 128, fmt)      # 1-bit: white where gray >= 128
+    both(hip, oracle, FC.black_scene_case())
 
 
 @pytest.mark.parametrize("fmt", FORMATS)
-@pytest.mark.parametrize("band", [(0, 40, 0, 700), (0, 600, 0, 25), (560, 600, 100, 300),
-                                  (0, 30, 200, 400)])
+@pytest.mark.parametrize("band", FC.BLACK_BANDS)
 def test_blackfilter_bands(hip, oracle, fmt, band):
-    h = band_page(600, 700, fmt, band, seed=8)
-    p = black_params(oracle, exclusions=[(150, 175, 449, 524)])
-    both(hip, oracle, h, lambda d: hip.blackfilter(d, p), lambda o: oracle.blackfilter(o, p))
+    both(hip, oracle, FC.black_band_case(fmt, band))
 
 
-@pytest.mark.parametrize("intensity", [20, 1, 3])
-@pytest.mark.parametrize("size", [(300, 400), (123, 77)])
+@pytest.mark.parametrize("intensity", FC.BLACK_IRREGULAR_INTENSITIES)
+@pytest.mark.parametrize("size", FC.BLACK_IRREGULAR_SIZES)
 def test_blackfilter_irregular(hip, oracle, intensity, size):
-    # dark blobs with holes, gaps and stray strokes: the fill order matters
-    rng = np.random.default_rng(intensity + size[0])
-    w, hh = size
-    g = np.full((hh, w), 255, np.uint8)
-    g[:, :12] = rng.integers(0, 40, size=(hh, 12))
-    for _ in range(40):
-        y, x = int(rng.integers(0, hh)), int(rng.integers(0, 30))
-        g[y:y + int(rng.integers(1, 5)), x:x + int(rng.integers(1, 25))] = rng.integers(0, 200)
-    g[rng.random((hh, w)) < 0.02] = 0
-    h = HostImage.from_array(g, A.FMT_GRAY8)
-    p = black_params(oracle, intensity=intensity, depth=(100, 100))
-    both(hip, oracle, h, lambda d: hip.blackfilter(d, p), lambda o: oracle.blackfilter(o, p))
+    both(hip, oracle, FC.black_irregular_case(intensity, size))
 
 
-def as_format(g, fmt, rng, thr=None):
-    """A gray array in `fmt`: RGB24 channels tinted apart (as the C4 pages),
-    Y400A with a random alpha."""
-    kw = {} if thr is None else {"abs_black_threshold": thr}
-    if fmt == A.FMT_RGB24:
-        t = rng.integers(0, 9, size=3)
-        rgb = np.stack([np.maximum(g.astype(int) - int(t[c]), 0) for c in range(3)], axis=2)
-        return HostImage.from_array(rgb.astype(np.uint8), fmt, **kw)
-    if fmt == A.FMT_Y400A:
-        a = rng.integers(0, 256, size=g.shape, dtype=np.uint8)
-        return HostImage.from_array(np.stack([g, a], axis=2), fmt, **kw)
-    return HostImage.from_array(g, fmt, **kw)
-
-
-def speck_page(w, h, density, seed, band=(5, 25)):
-    """A dark band for the bars to find, and dark specks a fill line can
-    reach through up to intensity-1 light pixels: the pattern of the heavy
-    C4 sheets, where one fill percolates through the page's salt specks."""
-    rng = np.random.default_rng(seed)
-    g = np.full((h, w), 255, np.uint8)
-    g[:, band[0]:band[1]] = rng.integers(0, 12, size=(h, band[1] - band[0]))
-    m = rng.random((h, w)) < density
-    g[m] = rng.integers(0, 60, size=int(m.sum()))
-    return g, rng
-
-
-@pytest.mark.parametrize("fmt", [A.FMT_GRAY8, A.FMT_RGB24, A.FMT_Y400A])
-@pytest.mark.parametrize("density,intensity", [(0.08, 20), (0.2, 6), (0.1, 30)])  # 383, 687, 3818 frames
+@pytest.mark.parametrize("fmt", BYTE_FORMATS)
+@pytest.mark.parametrize("density,intensity", FC.BLACK_PERCOLATION)  # 383, 687, 3818 frames
 def test_blackfilter_percolation(hip, oracle, fmt, density, intensity):
-    # thousands of short frames, most with several matching neighbours: the
-    # replay's resume-past-the-windows rule and its stack run every path
-    g, rng = speck_page(400, 300, density, seed=int(density * 1000) + intensity)
-    h = as_format(g, fmt, rng)
-    p = black_params(oracle, intensity=intensity, depth=(100, 100))
-    both(hip, oracle, h, lambda d: hip.blackfilter(d, p), lambda o: oracle.blackfilter(o, p))
+    both(hip, oracle, FC.black_percolation_case(fmt, density, intensity))
 
 
-@pytest.mark.parametrize("intensity", [0, 63, 64, 65, 1000])
+@pytest.mark.parametrize("intensity", FC.BLACK_INTENSITY_EDGES)
 def test_blackfilter_intensity_edges(hip, oracle, intensity):
-    # 0: the counter is 0 after the first position whatever it holds (every
-    # line empty); 63 / 64 / 65: the window's run test switches from the
-    # in-window smear to the cross-window carry; 1000: lines run to the edge
-    g, rng = speck_page(300, 200, 0.05, seed=intensity)
-    h = as_format(g, A.FMT_GRAY8, rng)
-    p = black_params(oracle, intensity=intensity, depth=(100, 100))
-    both(hip, oracle, h, lambda d: hip.blackfilter(d, p), lambda o: oracle.blackfilter(o, p))
+    both(hip, oracle, FC.black_intensity_case(intensity))
 
 
 @pytest.mark.parametrize("fmt", [A.FMT_GRAY8, A.FMT_RGB24])
 def test_blackfilter_long_lines(hip, oracle, fmt):
-    # fill lines over 1024 positions (several round trips a line) and
-    # neighbour runs over 512 (several check windows), in both directions
-    g, rng = speck_page(2600, 1300, 0.01, seed=7, band=(0, 30))
-    g[600:606, :] = rng.integers(0, 20, size=(6, 2600))   # a row band across the page
-    g[:, 1800:1804] = rng.integers(0, 20, size=(1300, 4))  # a column band down it
-    h = as_format(g, fmt, rng)
-    p = black_params(oracle, intensity=20, depth=(200, 200))
-    both(hip, oracle, h, lambda d: hip.blackfilter(d, p), lambda o: oracle.blackfilter(o, p))
+    both(hip, oracle, FC.black_long_lines_case(fmt))
 
 
-@pytest.mark.parametrize("thr", [0, 30, 254])
+@pytest.mark.parametrize("thr", FC.BLACK_MASK_MAX)
 def test_blackfilter_mask_max(hip, oracle, thr):
-    # the image's abs_black_threshold is the fill's match bound (fill.c:85):
-    # 0 matches only black, 254 everything but white
-    g, rng = speck_page(300, 200, 0.05, seed=thr + 1)
-    g[rng.random(g.shape) < 0.3] = rng.integers(0, 255)
-    h = as_format(g, A.FMT_GRAY8, rng, thr=thr)
-    p = black_params(oracle, intensity=8, depth=(100, 100), thr=200)
-    both(hip, oracle, h, lambda d: hip.blackfilter(d, p), lambda o: oracle.blackfilter(o, p))
+    both(hip, oracle, FC.black_mask_max_case(thr))
+
+
+@pytest.mark.parametrize("fmt", BYTE_FORMATS)
+def test_blackfilter_two_fills(hip, oracle, fmt):
+    both(hip, oracle, FC.black_two_fills_case(fmt))
+
+
+@pytest.mark.parametrize("fmt", BYTE_FORMATS)
+def test_blackfilter_short_lines_sheet(hip, oracle, fmt):
+    both(hip, oracle, FC.black_short_case(fmt))
+
+
+@pytest.mark.parametrize("stairs", FC.BLACK_STAIRS, ids=[s[0] for s in FC.BLACK_STAIRS])
+def test_blackfilter_stack_spill(hip, oracle, stairs):
+    both(hip, oracle, FC.black_stairs_case(*stairs))
+
+
+def test_blackfilter_stack_spill_short_lines_sheet(hip, oracle):
+    both(hip, oracle, FC.black_stairs_short_case())
+
+
+# ------------------------------------------------------------------ axis sums
+@pytest.mark.parametrize("fmt,size,arm", FC.AXIS_PAGES, ids=[a[2] + "-" + FC.NAMES[a[0]]
+                                                             for a in FC.AXIS_PAGES])
+def test_axis_sum_arms(hip, oracle, fmt, size, arm):
+    for case in FC.axis_cases(fmt, size, arm):
+        both(hip, oracle, case)
 
 
 # ---------------------------------------------------------- rotation detection

@@ -90,6 +90,18 @@ def test_default_gray_batch(hip, oracle):
     check(oracle, opts, sheets, "default")
 
 
+def test_gray_batch_grayfilter_wipes(hip, oracle):
+    # pages whose blank paper is light-gray clouds: the grayfilter wipes most
+    # tiles, and the mask detection after it takes the column sums the
+    # grayfilter kept up to date while wiping (k_gray_wipe's colsum, batch
+    # only).  test_filter_cases.py checks that the oracle's sheets differ
+    # without the grayfilter.
+    import filter_cases as FC
+    opts = oracle.default_options()
+    sheets = [[FC.gray_sheet_page(p)] for p in FC.GRAY_SHEET_PAGES]
+    check(oracle, opts, sheets, "gray clouds")
+
+
 def test_default_rgb_batch(hip, oracle):
     opts = oracle.default_options()
     sheets = [[synth(*SMALL, p, A.FMT_RGB24)] for p in (1, 3, 4)]

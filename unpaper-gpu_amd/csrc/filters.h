@@ -50,6 +50,21 @@ size_t gray_scratch_bytes(const GrayGeom& g);  // per sheet
 bool launch_grayfilter(const PlaneRef& img, const GrayGeom& g, void* scratch,
                        int64_t scratch_stride, int count, hipStream_t st,
                        uint32_t* colsum = nullptr, int64_t colsum_stride = 0);
+// The launcher's choices.  Cells: k_gray_cells_g (a gray plane by strips of
+// cell rows: 16-bit column lanes, a block as wide as the row) or the generic
+// k_gray_cells<FMT>.
+constexpr int kGrayStripMaxW = 16384;
+constexpr int kGrayMaxCh = 255;
+inline bool gray_cells_by_strips(const GrayGeom& g, int fmt) {
+  return fmt == F_GRAY8 && g.W <= kGrayStripMaxW && g.ch <= kGrayMaxCh;
+}
+// Tiles: k_gray_tiles_rows (a tile row's th cell rows staged in LDS) where
+// those rows fit kGrayRowLds, else k_gray_tiles.
+constexpr int kGrayRowLds = 32 * 1024;
+inline size_t gray_rows_lds(const GrayGeom& g) {
+  return 2 * sizeof(uint32_t) * (size_t)g.th * g.ncx;
+}
+inline bool gray_tiles_in_lds(const GrayGeom& g) { return gray_rows_lds(g) <= (size_t)kGrayRowLds; }
 
 // ---- blurfilter (filters.c:149-232) -------------------------------------
 struct BlurGeom {
@@ -68,6 +83,45 @@ size_t blur_scratch_bytes(const BlurGeom& g);
 // SheetBits::bbits: the one condition for making the plane and for reading it
 // (it stays exact only while every clear makes a pixel > white).
 bool blur_bits_usable(const BlurGeom& g, int fmt);
+// The launcher's choices.  Counts: from the bit-plane (have_bits: the caller
+// holds SheetBits::bbits and blur_bits_usable), k_blur_counts_g on a gray
+// plane (<true> with 16-byte aligned rows, `aligned16`), or the generic
+// k_blur_counts<FMT>; none for an image below one block.
+enum BlurCountsArm : int32_t {
+  BLUR_COUNTS_NONE,
+  BLUR_COUNTS_BITS,
+  BLUR_COUNTS_GRAY_V16,
+  BLUR_COUNTS_GRAY,
+  BLUR_COUNTS_GENERIC,
+};
+inline BlurCountsArm blur_counts_arm(const BlurGeom& g, int fmt, bool have_bits, bool aligned16) {
+  if (have_bits) return BLUR_COUNTS_BITS;
+  if (g.nrect <= 0) return BLUR_COUNTS_NONE;
+  if (fmt == F_GRAY8 && g.sh <= 65535 && g.W <= (1 << 16))
+    return aligned16 ? BLUR_COUNTS_GRAY_V16 : BLUR_COUNTS_GRAY;
+  return BLUR_COUNTS_GENERIC;
+}
+// Resolve: one wave holding a block row in lanes (k_blur_resolve_w; <true>
+// works a row of 33 .. 112 blocks in chunks), else k_blur_resolve: one lane
+// over the counts staged in LDS where they fit the 64 KiB every launch may
+// ask for, else over the counts in HBM.
+constexpr int kBlurLanesMax = 120;  // bpr + 8 entries of A in two VGPRs
+constexpr size_t kBlurResolveLds = 64 * 1024;
+enum BlurResolveArm : int32_t {
+  BLUR_RESOLVE_WAVE,
+  BLUR_RESOLVE_WAVE_CHUNKED,
+  BLUR_RESOLVE_GENERIC,
+  BLUR_RESOLVE_GENERIC_HBM,
+};
+inline size_t blur_resolve_lds(const BlurGeom& g) {
+  return sizeof(uint64_t) * ((size_t)g.nrect + 3 * (size_t)(g.bpr + 2));
+}
+inline BlurResolveArm blur_resolve_arm(const BlurGeom& g) {
+  const bool scalar = g.bpr >= 1 && g.bpr + 8 <= kBlurLanesMax && (int64_t)g.sw * g.sh < (1ll << 31);
+  if (scalar && g.bpr > 32 && g.bpr <= 112) return BLUR_RESOLVE_WAVE_CHUNKED;
+  if (scalar) return BLUR_RESOLVE_WAVE;
+  return blur_resolve_lds(g) <= kBlurResolveLds ? BLUR_RESOLVE_GENERIC : BLUR_RESOLVE_GENERIC_HBM;
+}
 void launch_blurfilter(const PlaneRef& img, const BlurGeom& g, void* scratch,
                        int64_t scratch_stride, int count, hipStream_t st, const SheetBits& bits);
 
@@ -90,6 +144,19 @@ void launch_noisefilter(const PlaneRef& img, const NoiseGeom& g, void* scratch,
                         const SheetBits& bits);
 // 32-pixel words per row of the GRAY8 bit-planes
 inline int32_t noise_bit_words(int32_t W) { return (W + 31) >> 5; }
+// The launcher's choices.  k_noise_group's block: large sheets (C4's 9920 x
+// 7016 double pages: several thousand triggers a sheet, never next to the
+// code-block decode) keep 1024 threads and 16384 triggers in LDS.
+inline int noise_group_threads(int32_t W, int32_t H) {
+  return (int64_t)W * H > (16 << 20) ? 1024 : 256;
+}
+// Its row buckets: kNoiseBuckets of 2^shift rows each.
+constexpr int kNoiseBuckets = 4096;
+__host__ __device__ inline int noise_bucket_shift(int32_t H) {
+  int b = 0;
+  while (((H - 1) >> b) >= kNoiseBuckets) b++;
+  return b;
+}
 
 // ---- blackfilter (filters.c:49-127, fill.c) -----------------------------
 struct BlackBar {
@@ -115,6 +182,11 @@ size_t black_scratch_bytes(const BlackGeom& g);
 void launch_blackfilter(const PlaneRef& img, const BlackGeom& g, const BlackBar* bars, void* scratch,
                         int64_t ss, SheetCtl* ctl, int count, hipStream_t st, const AxisArgs* hargs,
                         const AxisArgs* vargs, const SheetBits& bits);
+// The launcher's choice of k_black_resolve<FMT, LONG>: the long-line machinery
+// up to 16 Mpixel a sheet (kernels_black.hip, launch_black_t).
+inline bool black_resolve_long(const BlackGeom& g) { return (int64_t)g.W * g.H <= (16 << 20); }
+// The lowest frames of the resolve's DFS stack live in LDS, deeper ones in HBM.
+constexpr int kStackLds = 1024;
 // The blackfilter's row-major match plane (RM: bit x of row y = gray <=
 // mask_max, 64-bit words, black_wpr words a row) of sheet 0 inside its
 // scratch; sheet s at + s * scratch_stride bytes.

@@ -279,7 +279,6 @@ __device__ __forceinline__ uint64_t lane_range(int lo, int n) {
   return (n >= 64 ? ~0ull : ((1ull << n) - 1)) << lo;
 }
 
-constexpr int kStackLds = 1024;  // the lowest frames of the DFS stack live in LDS
 constexpr size_t kStackLdsBytes = (size_t)kStackLds * 32;  // 32 KiB: deeper frames go to HBM
 
 struct Frame {
@@ -1108,7 +1107,7 @@ static void launch_black_t(const PlaneRef& img, const BlackGeom& g, const BlackB
   // columns) 877 -> ~540 us a 64-sheet launch, while on C4's 70-Mpixel sheets
   // (floods percolating through specks: ~17k short crosses) its register
   // pressure made every frame slower (heaviest sheet 75 -> 88 ms).
-  const bool longl = (int64_t)g.W * g.H <= (16 << 20);
+  const bool longl = black_resolve_long(g);
   if (!(diag_skip() & 1)) {
     if (longl) {
       allow_dynamic_lds((const void*)k_black_resolve<FMT, true>, kStackLdsBytes);

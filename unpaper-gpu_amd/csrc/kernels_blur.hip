@@ -30,8 +30,14 @@ bool blur_geometry(int32_t W, int32_t H, const UphipBlurfilterParameters& p, uin
   return true;
 }
 
+// Per sheet: [nrect] u32 counts, [T * bpr] wipe flags, then k_blur_resolve's
+// three count rows for the geometries whose counts do not fit LDS.
+UPH_HD size_t blur_rows_off(const BlurGeom& g) {
+  const size_t b = (size_t)g.nrect * 4 + (size_t)g.T * (g.bpr > 0 ? g.bpr : 1);
+  return (b + 7) & ~(size_t)7;
+}
 size_t blur_scratch_bytes(const BlurGeom& g) {
-  size_t b = (size_t)g.nrect * 4 + (size_t)g.T * (g.bpr > 0 ? g.bpr : 1);
+  const size_t b = blur_rows_off(g) + sizeof(uint64_t) * 3 * (size_t)(g.bpr + 2);
   return (b + 255) & ~(size_t)255;
 }
 
@@ -204,6 +210,10 @@ __global__ void __launch_bounds__(256) k_blur_counts(PlaneRef img, BlurGeom g, u
   }
 }
 
+// IN_LDS: the counts and the three rows staged in LDS; else (more counted
+// rectangles than LDS holds: blur_resolve_arm) the counts read where they are
+// and the rows in the sheet's scratch.
+template <bool IN_LDS>
 __global__ void __launch_bounds__(256) k_blur_resolve(BlurGeom g, uint8_t* scratch,
                                                       int64_t sstride) {
   const int s = blockIdx.x;
@@ -211,9 +221,10 @@ __global__ void __launch_bounds__(256) k_blur_resolve(BlurGeom g, uint8_t* scrat
   uint8_t* wipe = scratch + s * sstride + (size_t)g.nrect * 4;
   extern __shared__ uint64_t sh[];  // [nrect] counts + [3*(bpr+2)] buffers
   uint64_t* cnt = sh;
-  uint64_t* buf = sh + g.nrect;
+  uint64_t* buf = IN_LDS ? sh + g.nrect : (uint64_t*)(scratch + s * sstride + blur_rows_off(g));
   const int32_t nbuf = 3 * (g.bpr + 2);
-  for (int32_t i = threadIdx.x; i < g.nrect; i += blockDim.x) cnt[i] = counts[i];
+  if (IN_LDS)
+    for (int32_t i = threadIdx.x; i < g.nrect; i += blockDim.x) cnt[i] = counts[i];
   for (int32_t i = threadIdx.x; i < nbuf; i += blockDim.x) buf[i] = 0;
   for (int32_t i = threadIdx.x; i < g.T * g.bpr; i += blockDim.x) wipe[i] = 0;
   __syncthreads();
@@ -225,12 +236,13 @@ __global__ void __launch_bounds__(256) k_blur_resolve(BlurGeom g, uint8_t* scrat
   buf[oc + bpr] = total;
   buf[on + 0] = total;
   buf[on + bpr] = total;
-  for (int32_t b = 0; b < bpr; b++) buf[oc + 1 + b] = cnt[b];
+  const auto count = [&](int32_t i) -> uint64_t { return IN_LDS ? cnt[i] : (uint64_t)counts[i]; };
+  for (int32_t b = 0; b < bpr; b++) buf[oc + 1 + b] = count(b);
   for (int32_t t = 0; t < g.T; t++) {
     const int32_t base = bpr + t * (bpr + 1);
-    buf[on + 0] = cnt[base + 0];
+    buf[on + 0] = count(base + 0);
     for (int32_t block = 1; block <= bpr; block++) {
-      buf[on + block + 1] = cnt[base + block];
+      buf[on + block + 1] = count(base + block);
       const uint64_t a = buf[op + block - 1], b = buf[op + block + 1], c = buf[oc + block];
       const uint64_t m1 = a > b ? (a > c ? a : c) : (b > c ? b : c);
       const uint64_t d = buf[on + block - 1], e = buf[on + block + 1];
@@ -261,7 +273,6 @@ __global__ void __launch_bounds__(256) k_blur_resolve(BlurGeom g, uint8_t* scrat
 //   (2,0,1): next[k+1] = A[k+2]; A[k+1], A[k+3], A[k] (twice);          wipe A[k]
 // and the float test ((float)max / total <= intensity) is monotone in max, so
 // it is the integer compare max <= tmax with tmax found once per sheet.
-constexpr int kBlurLanesMax = 120;  // bpr + 8 entries of A in two VGPRs
 __device__ __forceinline__ uint32_t umax(uint32_t a, uint32_t b) { return a > b ? a : b; }
 __device__ __forceinline__ uint32_t lane_get(uint32_t v, int32_t l) {
   return (uint32_t)__builtin_amdgcn_readlane((int32_t)v, l);
@@ -622,26 +633,35 @@ static void launch_blur_t(const PlaneRef& img, const BlurGeom& g, uint8_t* scr, 
   const auto a16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
   const bool v16 = img.P.pitch % 16 == 0 && img.P.stride % 16 == 0 && img.P.pitch >= ((g.W + 15) & ~15) &&
                    a16(img.P.base[0]) && a16(img.P.base[1]);
-  if (bbits)  // blur_bits_usable
-    UPH_LAUNCH_DIAG(64, k_blur_counts_bits, dim3(1 + g.T, count), dim3(256),
-                    4 * (size_t)(g.bpr + 2), st, g, bbits, bb_stride, scr, ss);
-  else if (g.nrect > 0 && FMT == F_GRAY8 && g.sh <= 65535 && g.W <= (1 << 16) && v16)
-    UPH_LAUNCH_DIAG(64, k_blur_counts_g<true>, dim3(1 + g.T, count), dim3(256),
-                    2 * (size_t)((g.W + 3) & ~3), st, img, g, scr, ss);
-  else if (g.nrect > 0 && FMT == F_GRAY8 && g.sh <= 65535 && g.W <= (1 << 16))
-    UPH_LAUNCH_DIAG(64, k_blur_counts_g<false>, dim3(1 + g.T, count), dim3(256),
-                    2 * (size_t)((g.W + 3) & ~3), st, img, g, scr, ss);
-  else if (g.nrect > 0)
-    hipLaunchKernelGGL(k_blur_counts<FMT>, dim3(g.nrect, count), dim3(256), 0, st, img, g, scr, ss);
-  const size_t lds = sizeof(uint64_t) * ((size_t)g.nrect + 3 * (size_t)(g.bpr + 2));
-  const bool scalar = g.bpr >= 1 && g.bpr + 8 <= kBlurLanesMax && (int64_t)g.sw * g.sh < (1ll << 31);
+  switch (blur_counts_arm(g, FMT, bbits != nullptr, v16)) {
+    case BLUR_COUNTS_BITS:  // blur_bits_usable
+      UPH_LAUNCH_DIAG(64, k_blur_counts_bits, dim3(1 + g.T, count), dim3(256),
+                      4 * (size_t)(g.bpr + 2), st, g, bbits, bb_stride, scr, ss);
+      break;
+    case BLUR_COUNTS_GRAY_V16:
+      UPH_LAUNCH_DIAG(64, k_blur_counts_g<true>, dim3(1 + g.T, count), dim3(256),
+                      2 * (size_t)((g.W + 3) & ~3), st, img, g, scr, ss);
+      break;
+    case BLUR_COUNTS_GRAY:
+      UPH_LAUNCH_DIAG(64, k_blur_counts_g<false>, dim3(1 + g.T, count), dim3(256),
+                      2 * (size_t)((g.W + 3) & ~3), st, img, g, scr, ss);
+      break;
+    case BLUR_COUNTS_GENERIC:
+      hipLaunchKernelGGL(k_blur_counts<FMT>, dim3(g.nrect, count), dim3(256), 0, st, img, g, scr, ss);
+      break;
+    case BLUR_COUNTS_NONE: break;
+  }
+  const BlurResolveArm resolve = blur_resolve_arm(g);
   if (diag_skip() & 8) {
-  } else if (scalar && g.bpr > 32 && g.bpr <= 112) {
+  } else if (resolve == BLUR_RESOLVE_WAVE_CHUNKED) {
     hipLaunchKernelGGL(k_blur_resolve_w<true>, dim3(count), dim3(64), 0, st, g, scr, ss);
-  } else if (scalar) {
+  } else if (resolve == BLUR_RESOLVE_WAVE) {
     hipLaunchKernelGGL(k_blur_resolve_w<false>, dim3(count), dim3(64), 0, st, g, scr, ss);
+  } else if (resolve == BLUR_RESOLVE_GENERIC) {
+    hipLaunchKernelGGL(k_blur_resolve<true>, dim3(count), dim3(256), blur_resolve_lds(g), st, g, scr,
+                       ss);
   } else {
-    hipLaunchKernelGGL(k_blur_resolve, dim3(count), dim3(256), lds, st, g, scr, ss);
+    hipLaunchKernelGGL(k_blur_resolve<false>, dim3(count), dim3(256), 0, st, g, scr, ss);
   }
   if (g.T * g.bpr > 0)
     hipLaunchKernelGGL(k_blur_wipe<FMT>, dim3(g.T * g.bpr, count), dim3(256), 0, st, img, g, scr,

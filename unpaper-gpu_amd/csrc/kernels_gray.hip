@@ -123,9 +123,7 @@ __global__ void __launch_bounds__(256) k_gray_cells(PlaneRef img, GrayGeom g, ui
 // the image the grayfilter leaves; k_gray_wipe adds what its wipes change), so
 // that scan needs no pass of its own.  kGrayStrips strips per block keep the
 // atomics at W per kGrayStrips * ch rows.
-constexpr int kGrayStripMaxW = 16384;
 constexpr int kGrayStrips = 8;
-constexpr int kGrayMaxCh = 255;
 __global__ void __launch_bounds__(1024) k_gray_cells_g(PlaneRef img, GrayGeom g, uint8_t* scratch,
                                                        int64_t sstride, uint32_t* colsum,
                                                        int64_t colsum_stride) {
@@ -326,7 +324,6 @@ __global__ void __launch_bounds__(256) k_gray_tiles(GrayGeom g, uint8_t* scratch
 // (dark counts and lightness sums) staged in LDS once instead of every tile
 // reading its tw x th cells from the scratch (the host takes it when those
 // rows fit kGrayRowLds).
-constexpr int kGrayRowLds = 32 * 1024;
 __global__ void __launch_bounds__(256) k_gray_tiles_rows(GrayGeom g, uint8_t* scratch,
                                                          int64_t sstride) {
   const int s = blockIdx.y;
@@ -432,7 +429,7 @@ template <int FMT>
 static bool launch_gray_t(const PlaneRef& img, const GrayGeom& g, uint8_t* scr, int64_t ss,
                           int count, hipStream_t st, uint32_t* colsum, int64_t cs) {
   dim3 grid((g.ncx + 255) / 256, g.ncy, count);
-  const bool strips = FMT == F_GRAY8 && g.W <= kGrayStripMaxW && g.ch <= kGrayMaxCh;
+  const bool strips = gray_cells_by_strips(g, FMT);
   if (!strips) colsum = nullptr;
   if (strips) {
     const size_t wq = (size_t)((g.W + 7) & ~7);
@@ -446,9 +443,9 @@ static bool launch_gray_t(const PlaneRef& img, const GrayGeom& g, uint8_t* scr, 
     hipLaunchKernelGGL(k_gray_cells<FMT>, grid, dim3(256), 0, st, img, g, scr, ss);
   }
   const int32_t ntiles = g.ntx * g.nty;
-  const size_t rows_lds = 2 * sizeof(uint32_t) * (size_t)g.th * g.ncx;
-  if (rows_lds <= (size_t)kGrayRowLds)
-    hipLaunchKernelGGL(k_gray_tiles_rows, dim3(g.nty, count), dim3(256), rows_lds, st, g, scr, ss);
+  if (gray_tiles_in_lds(g))
+    hipLaunchKernelGGL(k_gray_tiles_rows, dim3(g.nty, count), dim3(256), gray_rows_lds(g), st, g, scr,
+                       ss);
   else
     hipLaunchKernelGGL(k_gray_tiles, dim3((ntiles + 255) / 256, count), dim3(256), 0, st, g, scr,
                        ss);

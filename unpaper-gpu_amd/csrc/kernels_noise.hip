@@ -62,10 +62,6 @@ static int32_t noise_bit_words(const NoiseGeom& g) { return noise_bit_words(g.W)
 
 // k_noise_group keeps up to 16 triggers a thread in LDS (more: in HBM)
 constexpr int kCapPerThread = 16;
-// Large sheets (C4's 9920 x 7016 double pages: several thousand triggers a
-// sheet, never next to the code-block decode) keep 1024 threads and 16384
-// triggers in LDS.
-static int group_threads(int32_t W, int32_t H) { return (int64_t)W * H > (16 << 20) ? 1024 : 256; }
 size_t noise_scratch_bytes(const NoiseGeom& g) {
   // lists + a global sort buffer for the rare > 8192-trigger sequential case;
   // the GRAY8 dark bit-plane and, behind it, the small bit-plane share the
@@ -74,7 +70,7 @@ size_t noise_scratch_bytes(const NoiseGeom& g) {
   // the two planes than for the sort)
   // (and k_noise_group's keys / roots / last, 3 x its LDS cap words)
   size_t sort = 4 * pow2_at_least((size_t)g.capacity);
-  const size_t cap3 = 12 * (size_t)kCapPerThread * (size_t)group_threads(g.W, g.H);
+  const size_t cap3 = 12 * (size_t)kCapPerThread * (size_t)noise_group_threads(g.W, g.H);
   if (sort < cap3) sort = cap3;
   const size_t bits = 2 * 4 * (size_t)noise_bit_words(g) * (size_t)g.H;
   return noise_list_bytes(g) + (sort > bits ? sort : bits);
@@ -1141,19 +1137,12 @@ static int replay_blocks(int count) {
 // k_noise_group.  No separate resolver launch: a kernel asking for 128 KiB
 // of LDS waits for a nearly idle CU even when all its blocks would exit.
 constexpr uint32_t kNoiseNothing = 0, kNoiseLds = 1, kNoiseBig = 2;
-constexpr int kNoiseBuckets = 4096;
 constexpr int kGroupBucketMax = 256;  // longer buckets: block-wide bitonic sort
 constexpr int kLongList = 64;         // long buckets remembered by id (else: all scanned)
 // keys, parents, bucket starts, the scan's wave sums + 3 words, the long
 // bucket list (all dynamic: allow_dynamic_lds raises the limit to 160 KiB)
 constexpr size_t group_lds(int threads) {
   return sizeof(uint32_t) * (2 * (size_t)(kCapPerThread * threads) + kNoiseBuckets + 1 + 16 + 3 + kLongList);
-}
-
-__device__ __forceinline__ int noise_bucket_shift(int32_t H) {
-  int b = 0;
-  while (((H - 1) >> b) >= kNoiseBuckets) b++;
-  return b;
 }
 
 // The literal raster scan of the sorted triggers by one wave (filters.c:
@@ -1573,7 +1562,7 @@ static void launch_noise_t(const PlaneRef& img, const NoiseGeom& g, uint8_t* scr
     UPH_LAUNCH_DIAG(131072, k_noise_classify<FMT>, grid, dim3(256), 0, st, img, gd, scr, ss, ctl);
   }
   hipLaunchKernelGGL(k_noise_apply<FMT>, dim3(64, count), dim3(256), 0, st, img, gd, scr, ss, ctl);
-  const int gt = group_threads(g.W, g.H);
+  const int gt = noise_group_threads(g.W, g.H);
   if (!(diag_skip() & 2)) {
     if (gt == 1024) {
       allow_dynamic_lds((const void*)k_noise_group<FMT, 1024>, group_lds(1024));

@@ -214,34 +214,37 @@ static void launch_axis_t(const PlaneRef& ref, const AxisArgs* args, int axis, i
                           int32_t span_y, uint32_t* out, int64_t out_stride, int count,
                           hipStream_t st) {
   if (span_x <= 0 || span_y <= 0) return;
-  if (FMT == F_GRAY8) {
-    if (axis == 0) {
+  switch (axis_arm(FMT, axis, span_x, span_y)) {
+    case AXIS_COLSUM_GRAY: {
       const int rpb = 256;  // k_colsum_g's 16-bit column lanes assume <= 256
       dim3 grid((span_x + 3 + 255) / 256, (span_y + rpb - 1) / rpb, count);
       hipLaunchKernelGGL((k_colsum_g<MEAS>), grid, dim3(256), 0, st, ref, args, out, out_stride,
                          rpb);
-    } else {
-      // lanes per row: the power of two covering a full-width row's vectors
-      // (the regions of one launch differ per sheet only in position)
-      const int nv = (span_x + 30) / 16;
-      int lg = 0;
-      while ((1 << lg) < nv && lg < 6) lg++;
+      break;
+    }
+    case AXIS_ROWSUM_GRAY:
+    case AXIS_ROWSUM_GRAY_WAVE: {
+      const int lg = rowsum_gray_lg(span_x);
       const int64_t rows_per_block = 256 >> lg;
       dim3 grid((unsigned)((span_y + rows_per_block - 1) / rows_per_block), 1, count);
       hipLaunchKernelGGL((k_rowsum_g<MEAS>), grid, dim3(256), 0, st, ref, args, out, out_stride,
                          lg);
+      break;
     }
-    return;
-  }
-  if (axis == 0) {
-    const int rpb = 64;
-    dim3 grid((span_x + kRedThreads - 1) / kRedThreads, (span_y + rpb - 1) / rpb, count);
-    hipLaunchKernelGGL((k_colsum<FMT, MEAS>), grid, dim3(kRedThreads), 0, st, ref, args, out,
-                       out_stride, rpb);
-  } else {
-    int gx = span_y > 2048 ? 2048 : span_y;
-    hipLaunchKernelGGL((k_rowsum<FMT, MEAS>), dim3(gx, 1, count), dim3(kRedThreads), 0, st, ref,
-                       args, out, out_stride);
+    case AXIS_COLSUM: {
+      const int rpb = 64;
+      dim3 grid((span_x + kRedThreads - 1) / kRedThreads, (span_y + rpb - 1) / rpb, count);
+      hipLaunchKernelGGL((k_colsum<FMT, MEAS>), grid, dim3(kRedThreads), 0, st, ref, args, out,
+                         out_stride, rpb);
+      break;
+    }
+    case AXIS_ROWSUM:
+    case AXIS_ROWSUM_STRIDE: {
+      const int gx = span_y > kRowsumMaxBlocks ? kRowsumMaxBlocks : span_y;
+      hipLaunchKernelGGL((k_rowsum<FMT, MEAS>), dim3(gx, 1, count), dim3(kRedThreads), 0, st, ref,
+                         args, out, out_stride);
+      break;
+    }
   }
 }
 

@@ -3,6 +3,8 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
+#include <string>
 #include <vector>
 
 #include "filters.h"
@@ -138,6 +140,81 @@ void uphip_noisefilter(UphipImage image0, uint64_t intensity, uint8_t min_white_
   UPH_HIP(hipStreamSynchronize(st));
   if (status) return (void)fail("noisefilter: candidate list overflow (status %d)", status);
   mp.finish();
+}
+
+// ---- the launchers' choices, for tests (host only) ------------------------
+static const char* const kArmNames[] = {
+    "black.resolve_long",   "black.resolve_short",
+    "noise.group_256",      "noise.group_1024",
+    "noise.buckets_rows",   "noise.buckets_shifted",
+    "gray.cells_strips",    "gray.cells_generic",
+    "gray.tiles_lds",       "gray.tiles_generic",
+    "blur.counts_bits",     "blur.counts_gray_v16",
+    "blur.counts_gray",     "blur.counts_generic",
+    "blur.resolve_wave",    "blur.resolve_wave_chunked",
+    "blur.resolve_generic", "blur.resolve_generic_hbm",
+    "axis.colsum_gray",     "axis.rowsum_gray",
+    "axis.rowsum_gray_wave", "axis.colsum",
+    "axis.rowsum",          "axis.rowsum_stride",
+};
+
+const char* uphip_filter_arm_names(void) {
+  static const std::string all = [] {
+    std::string a;
+    for (const char* n : kArmNames) a += (a.empty() ? "" : " ") + std::string(n);
+    return a;
+  }();
+  return all.c_str();
+}
+
+int32_t uphip_filter_arms(const char* filter, int32_t format, int32_t width, int32_t height,
+                          const void* params, uint8_t threshold, int32_t fused, char* out,
+                          size_t cap) {
+  if (!filter || !out || cap == 0 || width <= 0 || height <= 0) return -1;
+  // 1-bit frames are filtered through a GRAY8 proxy (mono_proxy.h)
+  const int fmt = format == UPHIP_FMT_RGB24 ? F_RGB24 : format == UPHIP_FMT_Y400A ? F_Y400A : F_GRAY8;
+  std::vector<const char*> arms;
+  const std::string f(filter);
+  if (f == "blackfilter") {
+    BlackGeom g{};
+    g.W = width;
+    g.H = height;
+    arms.push_back(black_resolve_long(g) ? "black.resolve_long" : "black.resolve_short");
+  } else if (f == "noisefilter") {
+    arms.push_back(noise_group_threads(width, height) == 1024 ? "noise.group_1024" : "noise.group_256");
+    arms.push_back(noise_bucket_shift(height) > 0 ? "noise.buckets_shifted" : "noise.buckets_rows");
+  } else if (f == "grayfilter") {
+    GrayGeom g;
+    if (!params || !gray_geometry(width, height, *(const UphipGrayfilterParameters*)params, threshold, &g))
+      return -1;
+    arms.push_back(gray_cells_by_strips(g, fmt) ? "gray.cells_strips" : "gray.cells_generic");
+    arms.push_back(gray_tiles_in_lds(g) ? "gray.tiles_lds" : "gray.tiles_generic");
+  } else if (f == "blurfilter") {
+    BlurGeom g;
+    if (!params || !blur_geometry(width, height, *(const UphipBlurfilterParameters*)params, threshold, &g))
+      return -1;
+    // frames and batch planes are allocated 256-byte aligned with a pitch of a
+    // multiple of 256: aligned16 holds for every plane the ABI can make
+    static const char* const counts[] = {nullptr, "blur.counts_bits", "blur.counts_gray_v16",
+                                         "blur.counts_gray", "blur.counts_generic"};
+    const char* c = counts[blur_counts_arm(g, fmt, fused && blur_bits_usable(g, fmt), true)];
+    if (c) arms.push_back(c);
+    static const char* const resolve[] = {"blur.resolve_wave", "blur.resolve_wave_chunked",
+                                          "blur.resolve_generic", "blur.resolve_generic_hbm"};
+    arms.push_back(resolve[blur_resolve_arm(g)]);
+  } else if (f == "axis") {
+    static const char* const axis[] = {"axis.colsum_gray", "axis.rowsum_gray", "axis.rowsum_gray_wave",
+                                       "axis.colsum",      "axis.rowsum",      "axis.rowsum_stride"};
+    arms.push_back(axis[axis_arm(fmt, 0, width, height)]);
+    arms.push_back(axis[axis_arm(fmt, 1, width, height)]);
+  } else {
+    return -1;
+  }
+  std::string s;
+  for (const char* a : arms) s += (s.empty() ? "" : " ") + std::string(a);
+  if (s.size() + 1 > cap) return -1;
+  memcpy(out, s.c_str(), s.size() + 1);
+  return (int32_t)arms.size();
 }
 
 void uphip_blackfilter(UphipImage image0, UphipBlackfilterParameters params) {

@@ -45,6 +45,33 @@ struct BorderEdgeArgs {
 void launch_axis_reduce(const PlaneRef& ref, const AxisArgs* args, int axis, int meas,
                         int32_t span_x, int32_t span_y, uint32_t* out, int64_t out_stride,
                         int count, hipStream_t st);
+// Which kernel launch_axis_reduce takes (uphip_filter_arms reports it).
+enum AxisArm : int32_t {
+  AXIS_COLSUM_GRAY,    // k_colsum_g
+  AXIS_ROWSUM_GRAY,    // k_rowsum_g, 2^lg < 64 lanes a row
+  AXIS_ROWSUM_GRAY_WAVE,  // k_rowsum_g at lg = 6: a wave a row
+  AXIS_COLSUM,         // k_colsum<FMT>
+  AXIS_ROWSUM,         // k_rowsum<FMT>, a block a row
+  AXIS_ROWSUM_STRIDE,  // k_rowsum<FMT>, 2048 blocks striding over the rows
+};
+constexpr int32_t kRowsumMaxBlocks = 2048;
+// k_rowsum_g's lanes per row, as a power of two: the one covering a
+// full-width row's 16-byte vectors (the regions of one launch differ per sheet
+// only in position)
+inline int rowsum_gray_lg(int32_t span_x) {
+  const int nv = (span_x + 30) / 16;
+  int lg = 0;
+  while ((1 << lg) < nv && lg < 6) lg++;
+  return lg;
+}
+inline AxisArm axis_arm(int fmt, int axis, int32_t span_x, int32_t span_y) {
+  if (fmt == F_GRAY8) {
+    if (axis == 0) return AXIS_COLSUM_GRAY;
+    return rowsum_gray_lg(span_x) == 6 ? AXIS_ROWSUM_GRAY_WAVE : AXIS_ROWSUM_GRAY;
+  }
+  if (axis == 0) return AXIS_COLSUM;
+  return span_y > kRowsumMaxBlocks ? AXIS_ROWSUM_STRIDE : AXIS_ROWSUM;
+}
 // grid: jobs_per_sheet x count; results[s*jobs + j] = detect_edge count
 // max_extent: the largest EdgeArgs/BorderEdgeArgs extent of the launch
 void launch_edge_scan(const EdgeArgs* args, int jobs_per_sheet, const uint32_t* sums,

@@ -51,7 +51,7 @@ EXPORTED = [
     "uphip_sink_destroy", "uphip_runner_create", "uphip_runner_destroy",
     "uphip_runner_run_device", "uphip_runner_run_host", "uphip_runner_get_stats",
     "uphip_runner_output_info", "uphip_runner_batch", "uphip_runner_layout", "uphip_batch_device_bytes", "uphip_host_alloc", "uphip_host_free",
-    "uphip_check_libm", "uphip_jpeg_probe", "uphip_jpeg_read", "uphip_jpeg_decode",
+    "uphip_check_libm", "uphip_filter_arms", "uphip_filter_arm_names", "uphip_jpeg_probe", "uphip_jpeg_read", "uphip_jpeg_decode",
     "uphip_jpeg_entropy_decode", "uphip_runner_placement", "uphip_runner_slot_chunk",
     "uphip_jpeg_encode", "uphip_batch_encode_jpeg_async", "uphip_batch_jpeg_sizes",
     "uphip_batch_jpeg_download_async", "uphip_batch_jpeg_page", "uphip_sink_jpeg",
@@ -220,6 +220,9 @@ def load_library(path=LIB_PATH):
         "uphip_memcpy_htod": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
         "uphip_memcpy_dtoh": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
         "uphip_check_libm": (C.c_int, [C.c_uint32, C.POINTER(C.c_uint64)]),
+        "uphip_filter_arms": (C.c_int32, [C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                          C.c_uint8, C.c_int32, C.c_char_p, C.c_size_t]),
+        "uphip_filter_arm_names": (C.c_char_p, []),
         "uphip_runner_placement": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32),
                                              C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
         "uphip_jpeg_probe": (C.c_int, [C.c_char_p, C.POINTER(A.PnmInfo)]),
