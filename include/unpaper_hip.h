@@ -384,7 +384,7 @@ typedef struct UphipBatch UphipBatch;
 
 typedef struct {
   int32_t capacity;        /* sheets per batch */
-  int32_t page_width;      /* input page geometry (all pages) */
+  int32_t page_width;      /* input page geometry (all pages; the largest with uphip_batch_set_page_size) */
   int32_t page_height;
   int32_t page_format;     /* UphipPixelFormat of the inputs */
 } UphipBatchGeometry;
@@ -404,6 +404,18 @@ void *uphip_batch_input_ptr(UphipBatch *batch, int32_t slot, int64_t *pitch);
  * uphip_batch_wait or uphip_batch_query() == 1). */
 int uphip_batch_set_input(UphipBatch *batch, int32_t slot, const void *host,
                           int64_t linesize);
+/* The page in input slot `slot` is width x height pixels, rows at the slot's
+ * pitch from the slot's origin; both <= the batch geometry's page size, which
+ * becomes the slot's capacity.  0 x 0 puts the slot back to the geometry's
+ * size.  Holds for every later run until changed: uphip_batch_set_input copies
+ * the slot's own rows, and both runs centre every page in its part of the
+ * sheet by its slot's size (cropped where larger).  Needs options.sheet_size
+ * fully set (both != -1) and pre_rotate == 0; -1 and an error naming the
+ * field otherwise. */
+int uphip_batch_set_page_size(UphipBatch *batch, int32_t slot, int32_t width, int32_t height);
+/* Which decode the last run took: 0 copy (fill + k_copy), 1 fused plain
+ * (k_decode_gray), 2 fused fit (k_decode_gray_fit); -1 before any run. */
+int32_t uphip_batch_decode_route(UphipBatch *batch);
 /* Run the pipeline on sheets [0, count) whose pages sit in the batch's input
  * slots.  Asynchronous: returns after enqueueing; uphip_batch_wait() joins
  * and reports device-side failures. */
@@ -1003,6 +1015,12 @@ UphipSink *uphip_sink_jp2(const char *pattern, int64_t wrap);
 #define UPHIP_PDF_HIGH 1
 UphipSource *uphip_source_pdf(const char *path, int32_t dpi);
 int64_t uphip_source_page_count(UphipSource *source);
+/* The largest width, the largest height and the common format over all pages
+ * of a PNM-list, TIFF or PDF source (dpi as the source's): the geometry of a
+ * runner with a fully set sheet_size that takes them all.  Host only.  -1 and
+ * an error naming the first page of another format, or for callback / memory
+ * sources. */
+int uphip_source_max_geometry(UphipSource *source, UphipPnmInfo *info);
 UphipSink *uphip_sink_pdf(const char *path, const UphipPdfMetadata *meta, int32_t dpi,
                           int32_t quality, int32_t mode);
 /* Bilevel documents: for runners whose sheets leave as MONOWHITE (a bilevel

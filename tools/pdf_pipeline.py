@@ -5,14 +5,18 @@ out.pdf`), on the runner's PDF source and sink.
 
     python tools/pdf_pipeline.py in.pdf out.pdf [--pdf-quality fast|high]
         [--pdf-dpi N] [--jpeg-quality Q] [--input-pages 1|2] [--output-pages 1|2]
+        [--sheet-size WxH]
 
 Every input page is decoded where its codec runs (JPEG / JPEG 2000 on the
 device, JBIG2 / CCITT / Flate on the load pool), the sheets go through the
 default pipeline, and each output page is encoded on the device (JPEG, or
 lossless JPEG 2000 with --pdf-quality high) into one PDF with the input's
-metadata.  Pages must share the first page's image geometry (the runner's
-batches are of one page size); a page that does not is left out of the
-output, as the reference's page accumulator leaves out failed pages.
+metadata.  With --sheet-size WxH (the reference's --sheet-size, in pixels)
+the pages may be of any sizes: the runner is sized for the largest
+(uphip_source_max_geometry) and every page is centred in a W x H sheet,
+cropped where larger.  Without it the pages must share the first page's image
+geometry; a page that does not is left out of the output, as the reference's
+page accumulator leaves out failed pages.
 --pdf-dpi 0 (the default here) takes the page images as they are; a dpi
 applies the reference's size check (an image off the page size would need
 a rasteriser and fails).
@@ -29,7 +33,8 @@ sys.path.insert(0, os.path.join(ROOT, "unpaper-gpu_amd", "python"))
 from unpaper_hip import ctypes_abi as A  # noqa: E402
 from unpaper_hip import pdf as P  # noqa: E402
 from unpaper_hip.device import load_library  # noqa: E402
-from unpaper_hip.pipeline import Runner, sink_pdf, source_page_count, source_pdf  # noqa: E402
+from unpaper_hip.pipeline import (Runner, sink_pdf, source_max_geometry, source_page_count,  # noqa: E402
+                                  source_pdf)
 
 
 def main():
@@ -41,6 +46,7 @@ def main():
     ap.add_argument("--jpeg-quality", type=int, default=0, help="0 = 85 (PDF_OUTPUT_JPEG_QUALITY)")
     ap.add_argument("--input-pages", type=int, default=1, choices=(1, 2))
     ap.add_argument("--output-pages", type=int, default=1, choices=(1, 2))
+    ap.add_argument("--sheet-size", metavar="WxH", help="one sheet size in pixels: admits pages of any sizes")
     ap.add_argument("--sheets-per-batch", type=int, default=16)
     ap.add_argument("--streams", type=int, default=8)
     args = ap.parse_args()
@@ -54,6 +60,10 @@ def main():
     opts.input_count = args.input_pages
     opts.output_count = args.output_pages
     src = source_pdf(args.input, args.pdf_dpi)
+    if args.sheet_size:
+        sw, sh = (int(v) for v in args.sheet_size.lower().split("x"))
+        opts.sheet_size = A.RectangleSize(sw, sh)
+        w, h, fmt = source_max_geometry(src)
     npages = source_page_count(src)
     jobs = npages // args.input_pages
     snk = sink_pdf(args.output, meta, args.pdf_dpi if args.pdf_dpi else 0, args.jpeg_quality,

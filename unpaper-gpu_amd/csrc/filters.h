@@ -229,5 +229,13 @@ float combine_edge_rotations(const float* rot, int count, float deviation_rad);
 void launch_decode_gray(const uint8_t* src, int64_t spitch, int64_t sstride, const PlaneRef& dst,
                         uint8_t white, const SheetBits& bits, const BlackGeom& bg,
                         void* black_scratch, int64_t scratch_stride, int count, hipStream_t st);
+// The same with sheet s's page placed by place[s] (the clipped page area and
+// its target, as k_copy takes them) in a sheet of `background` bytes: the
+// sheet's fill, the copy and the planes in one pass.  bits.vsum is not served
+// (the blackfilter sums the sheet).  Same alignment conditions.
+void launch_decode_gray_fit(const uint8_t* src, int64_t spitch, int64_t sstride, const CopyArgs* place,
+                            uint8_t background, const PlaneRef& dst, uint8_t white, const SheetBits& bits,
+                            const BlackGeom& bg, void* black_scratch, int64_t scratch_stride, int count,
+                            hipStream_t st);
 
 }  // namespace uph

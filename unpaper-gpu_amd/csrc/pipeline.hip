@@ -125,12 +125,44 @@ void* uphip_batch_input_ptr(UphipBatch* b, int32_t slot, int64_t* pitch) {
   return b->inputs + (int64_t)slot * b->in_page_stride;
 }
 
+int uphip_batch_set_page_size(UphipBatch* b, int32_t slot, int32_t width, int32_t height) {
+  if (!b) return fail("batch_set_page_size: null batch"), -1;
+  if (b->o.sheet_size.width == -1 || b->o.sheet_size.height == -1)
+    return fail("batch_set_page_size: options.sheet_size must be fully set (it is %dx%d): without it every "
+                "sheet takes its size from its own page", b->o.sheet_size.width, b->o.sheet_size.height), -1;
+  if (b->o.pre_rotate != 0)
+    return fail("batch_set_page_size: options.pre_rotate is %d, per-slot page sizes need 0", b->o.pre_rotate), -1;
+  if (slot < 0 || slot >= b->cap * b->n_in)
+    return fail("batch_set_page_size: slot %d out of range (%d slots)", slot, b->cap * b->n_in), -1;
+  if ((width == 0) != (height == 0) || width < 0 || width > b->geo.page_width)
+    return fail("batch_set_page_size: width %d outside 1..%d (the geometry's page_width)", width,
+                b->geo.page_width), -1;
+  if (height < 0 || height > b->geo.page_height)
+    return fail("batch_set_page_size: height %d outside 1..%d (the geometry's page_height)", height,
+                b->geo.page_height), -1;
+  if (b->slot_w.empty()) {
+    if (width == 0) return 0;  // never sized: the plan's placements stand
+    b->slot_w.assign((size_t)b->cap * b->n_in, 0);
+    b->slot_h.assign((size_t)b->cap * b->n_in, 0);
+  } else if (b->slot_w[(size_t)slot] == width && b->slot_h[(size_t)slot] == height) {
+    return 0;  // nothing changes: the next run uploads nothing
+  }
+  b->slot_w[(size_t)slot] = width;
+  b->slot_h[(size_t)slot] = height;
+  batch_place(b);
+  return 0;
+}
+
+int32_t uphip_batch_decode_route(UphipBatch* b) { return b ? b->route : -1; }
+
 int uphip_batch_set_input(UphipBatch* b, int32_t slot, const void* host, int64_t linesize) {
   if (!b || slot < 0 || slot >= b->cap * b->n_in) return fail("batch_set_input: bad slot"), -1;
   hipSetDevice(b->device);
-  const int64_t rb = row_bytes(b->geo.page_width, b->geo.page_format);
+  const bool sized = !b->slot_w.empty() && b->slot_w[(size_t)slot];
+  const int32_t w = sized ? b->slot_w[(size_t)slot] : b->geo.page_width;
+  const int32_t h = sized ? b->slot_h[(size_t)slot] : b->geo.page_height;
   return UPH_HIP(hipMemcpy2DAsync(b->inputs + (int64_t)slot * b->in_page_stride, b->in_pitch, host,
-                                  linesize, rb, b->geo.page_height, hipMemcpyHostToDevice, b->st))
+                                  linesize, row_bytes(w, b->geo.page_format), h, hipMemcpyHostToDevice, b->st))
              ? 0
              : -1;
 }

@@ -100,8 +100,9 @@ struct BatchPlan {
 
 struct BatchArgs {
   struct {
-    Fill sheet;                    // the sheet's background where the pages leave some
-    Copy page[UPHIP_MAX_PAGES];    // the unfused decode's blits (center_image of each page)
+    Fill sheet;                    // the sheet's background, for the runs whose pages leave some
+    Copy page[UPHIP_MAX_PAGES];    // the decode's placements (center_image of each page): k_copy's
+                                   // blits, the fit decode's records
   } decode;
   struct {
     const MaskArgs* masks = nullptr;
@@ -205,6 +206,16 @@ struct UphipBatch {
   uint32_t* sums = nullptr;            // cap * sums_stride
   int64_t sums_stride = 0;
   int last_count = 0;
+  // A page size per input slot (uphip_batch_set_page_size): empty until the
+  // first call, then cap * n_in entries, 0 for the geometry's size.  `place`
+  // is the host mirror of args.decode.page[j].args, rebuilt by batch_place and
+  // uploaded by the next run when a size changed.
+  std::vector<int32_t> slot_w, slot_h;
+  std::vector<uph::CopyArgs> place[UPHIP_MAX_PAGES];
+  bool place_dirty = false;
+  int32_t identity_sheets = 0;  // sheets [0, n) whose page is the sheet unchanged
+  int32_t covered_sheets = 0;   // sheets [0, n) whose page leaves no background
+  int32_t route = -1;           // the last run's decode (uphip_batch_decode_route)
   // GPU JPEG output branch (uphip_batch_encode_jpeg_async)
   uph::JencContext* jenc = nullptr;
   int jenc_pages = 0;
@@ -225,6 +236,10 @@ namespace uph {
 bool batch_plan(UphipBatch* b);
 bool batch_allocate(UphipBatch* b);
 bool batch_prepare(UphipBatch* b);
+// a fully set sheet_size and no pre_rotate: the pages of a run may differ in size
+bool fixed_sheet(const UphipOptions& o);
+// the placements of every slot's page from slot_w / slot_h into b->place
+void batch_place(UphipBatch* b);
 // pipeline_run.hip: queues one run of `count` sheets read from src on b->st
 bool run_batch(UphipBatch* b, int count, const uint8_t* src, int64_t spitch, int64_t sstride);
 // the sources of a batch's output pages for the JPEG encode

@@ -510,6 +510,35 @@ void prepare_deskew(UphipBatch* b) {
 
 }  // namespace
 
+bool fixed_sheet(const UphipOptions& o) {
+  return o.sheet_size.width != -1 && o.sheet_size.height != -1 && o.pre_rotate == 0;
+}
+
+// Slot (s, j)'s page placed as batch_prepare places the geometry's: the same
+// center_image, of the slot's own size.  Only the records change; the plan,
+// the sheet and everything after the decode stay as planned.
+void batch_place(UphipBatch* b) {
+  const int n = b->n_in;
+  const int32_t sw = b->sheet_w, sh = b->sheet_h;
+  b->identity_sheets = b->covered_sheets = b->cap;
+  for (int j = 0; j < n; j++) {
+    b->place[j].resize((size_t)b->cap);
+    int32_t rows = 1;
+    for (int s = 0; s < b->cap; s++) {
+      const size_t q = (size_t)s * n + j;
+      const int32_t w = b->slot_w[q] ? b->slot_w[q] : b->geo.page_width;
+      const int32_t h = b->slot_h[q] ? b->slot_h[q] : b->geo.page_height;
+      const Placement p = center_in(w, h, sw * j / n, 0, sw / n, sh);
+      b->place[j][(size_t)s] = CopyArgs{clip(rect_from_size(p.sx, p.sy, p.w, p.h), w, h), p.tx, p.ty, 1};
+      rows = imax(rows, p.h);
+      if (n != 1 || w != sw || h != sh) b->identity_sheets = imin(b->identity_sheets, s);
+      if (n != 1 || w < sw || h < sh) b->covered_sheets = imin(b->covered_sheets, s);
+    }
+    b->args.decode.page[j].rows = rows;
+  }
+  b->place_dirty = true;
+}
+
 bool batch_prepare(UphipBatch* b) {
   const UphipOptions& o = b->o;
   const uint32_t dis = o.disable;
@@ -518,7 +547,7 @@ bool batch_prepare(UphipBatch* b) {
   // decode: the unfused blits are built whether or not a run will be fused
   // (that depends on the alignment of the pages a run is given)
   const int32_t sw = b->sheet_w, sh = b->sheet_h;
-  if (!b->plan.covered) A.decode.sheet = up.fill(Rect{0, 0, sw - 1, sh - 1}, o.sheet_background);
+  if (!b->plan.covered || fixed_sheet(o)) A.decode.sheet = up.fill(Rect{0, 0, sw - 1, sh - 1}, o.sheet_background);
   for (int j = 0; j < b->n_in; j++)  // center_image(page, sheet, (w*j/n, 0), (w/n, h))  (blit.c:175-202)
     A.decode.page[j] = up.copy(center_in(b->rp_w, b->rp_h, sw * j / b->n_in, 0, sw / b->n_in, sh), b->rp_w, b->rp_h);
   // pre and post (sheet_stages.c:187-325, :415-534)

@@ -1,7 +1,7 @@
 // pipeline_run.hip — one run of a batch: the control kernels (one thread per
 // sheet) and run_batch with its stage helpers.  Every size, flag and uniform
 // argument block comes from the plan (pipeline_plan.hip); a run only launches,
-// and its one branch on its own arguments is decode_fused.
+// and its one branch on its own arguments is the decode's route.
 #include <cstdio>
 #include <cstdlib>
 
@@ -508,17 +508,18 @@ void border_all(UphipBatch* b, int count, bool rows_ready, const MoveArgs* cente
   }
 }
 
-// The decode may also produce the noisefilter's dark bit-plane and the
-// blackfilter's v-stripe row sums (k_decode_gray) when a GRAY8 page becomes
-// the sheet unchanged and nothing writes the sheet between the decode and
-// the filters (sheet_stages.c:187-325: pre-mirror, -shift, -masks,
-// -stretch/size, -wipes, -border all off).  The alignment of the pages a run
-// is given decides with the options, so this is asked per run.
-bool decode_fused(const UphipBatch* b, const uint8_t* src, int64_t spitch, int64_t sstride) {
+// The decode may also produce the noisefilter's dark bit-plane, the
+// blurfilter's bit-plane and the blackfilter's match plane (k_decode_gray,
+// k_decode_gray_fit) when a GRAY8 page is placed in the sheet and nothing
+// writes the sheet between the decode and the filters (sheet_stages.c:187-325:
+// pre-mirror, -shift, -masks, -stretch/size, -wipes, -border all off).  The
+// alignment of the pages a run is given decides with the options, so this is
+// asked per run.
+bool decode_fusable(const UphipBatch* b, const uint8_t* src, int64_t spitch, int64_t sstride) {
   const UphipOptions& o = b->o;
   const uint32_t dis = o.disable;
   if (b->work_fmt != F_GRAY8 || b->geo.page_format != F_GRAY8 || b->n_in != 1) return false;
-  if (b->rp_w != b->sheet_w || b->rp_h != b->sheet_h || o.pre_rotate != 0) return false;
+  if (o.pre_rotate != 0) return false;
   if (b->sheet_w != b->W || b->sheet_h != b->H) return false;  // stretch / page size
   // 16-byte vector loads at src + s*sstride + y*spitch (a row's last vector
   // may read up to 15 bytes past the row within its pitch)
@@ -627,19 +628,39 @@ bool run_batch(UphipBatch* b, int count, const uint8_t* src, int64_t spitch, int
   // ---- decode: pages -> working sheet (sheet_stages.c:44-185) ----------
   const int n = b->n_in;  // pages a sheet
   const Planes S0 = planes_of(b, b->sheet_w, b->sheet_h);
-  const bool fused = decode_fused(b, src, spitch, sstride);
+  // the slots' page sizes, when a run was given some: their placements go up
+  // once per change, and decide with the plan which decode this run takes
+  const bool sized = !b->slot_w.empty();
+  if (sized && b->place_dirty) {
+    for (int j = 0; j < n; j++)
+      UPH_HIP(hipMemcpyAsync(const_cast<CopyArgs*>(A.decode.page[j].args), b->place[j].data(),
+                             sizeof(CopyArgs) * b->cap, hipMemcpyHostToDevice, b->st));
+    b->place_dirty = false;
+  }
+  const bool identity = sized ? count <= b->identity_sheets : plan.covered;
+  const bool covered = sized ? count <= b->covered_sheets : plan.covered;
+  const bool fused = decode_fusable(b, src, spitch, sstride);
+  b->route = !fused ? 0 : identity ? 1 : 2;
   SheetBits bits;  // what the fused decode hands on
   if (fused) {
     const bool black_on = !(dis & UPHIP_NO_BLACKFILTER) && b->bgeo.nbars > 0;
     bits.nbits = !(dis & UPHIP_NO_NOISEFILTER) ? b->nbits : nullptr;
     bits.bbits = !(dis & UPHIP_NO_BLURFILTER) ? b->bbits : nullptr;
     bits.stride = b->nbits_stride;
-    bits.vsum = black_on && b->bgeo.vregion.x1 >= b->bgeo.vregion.x0;
+    // the v-stripe sums are read from the pages, which are the sheet only
+    // under the identity: a placed sheet is summed by the blackfilter itself
+    bits.vsum = identity && black_on && b->bgeo.vregion.x1 >= b->bgeo.vregion.x0;
     bits.rm = black_on;
-    launch_decode_gray(src, spitch, sstride, cur_ref(S0, b->ctl), o.abs_white_threshold, bits,
-                       b->bgeo, b->scr, b->scr_stride, count, b->st);
+    if (identity)
+      launch_decode_gray(src, spitch, sstride, cur_ref(S0, b->ctl), o.abs_white_threshold, bits,
+                         b->bgeo, b->scr, b->scr_stride, count, b->st);
+    else
+      launch_decode_gray_fit(src, spitch, sstride, A.decode.page[0].args,
+                             gray_of(Px{o.sheet_background.r, o.sheet_background.g, o.sheet_background.b}),
+                             cur_ref(S0, b->ctl), o.abs_white_threshold, bits, b->bgeo, b->scr,
+                             b->scr_stride, count, b->st);
   }
-  fill(b, S0, 0, A.decode.sheet, count);
+  if (!fused && !covered) fill(b, S0, 0, A.decode.sheet, count);
   for (int j = 0; j < n && !fused; j++) {
     uint8_t* const page = const_cast<uint8_t*>(src) + j * sstride;
     Planes pg{{page, page}, spitch, sstride * n, b->geo.page_width, b->geo.page_height, b->geo.page_format, count};

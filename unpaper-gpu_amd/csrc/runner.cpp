@@ -285,6 +285,19 @@ struct HostRun {
 
 enum : int { FREE = 0, LOADING, LOADED, RUNNING, DRAINING, STORING };
 
+// A fixed-sheet run: the first npages pages of the slot's chunk placed by
+// their own sizes, every other input slot of the batch (all of them for a
+// source without sizes) back at the geometry's: no size outlives its chunk.
+bool place_pages(UphipRunner* r, Slot* sl, int npages) {
+  if (!r->fixed_sheet) return true;
+  for (int q = 0; q < r->geo.capacity * r->opts.input_count; q++) {
+    const PageSize ps = q < npages ? sl->psize[(size_t)q] : PageSize{};
+    const bool full = ps.w == r->geo.page_width && ps.h == r->geo.page_height;
+    if (uphip_batch_set_page_size(sl->b, q, full ? 0 : ps.w, full ? 0 : ps.h) != 0) return false;
+  }
+  return true;
+}
+
 // One device thread's slots in a host-fed run.  A slot moves FREE -> LOADING
 // (page tasks on the host pool) -> LOADED (last task) -> RUNNING (H2D +
 // pipeline queued on its stream) -> DRAINING (status read, D2H queued) ->
@@ -335,7 +348,10 @@ struct SlotLoop {
       if (sl->failed[(size_t)s]) {
         dc.failed++;
         if ((sl->failed[(size_t)s] & 2) && dc.error.empty()) dc.error = "a sheet could not be stored";
-        if ((sl->failed[(size_t)s] & 4) && dc.error.empty()) dc.error = "a page could not be loaded";
+        if ((sl->failed[(size_t)s] & 4) && dc.error.empty()) {
+          const std::string& why = sl->load_error[(size_t)s];
+          dc.error = why.empty() ? "a page could not be loaded" : "a page could not be loaded: " + why;
+        }
       } else {
         dc.done++;
       }
@@ -355,6 +371,8 @@ struct SlotLoop {
     sl->tdev = false;
     sl->count = (int32_t)std::min<int64_t>(S, run.njobs - first);
     sl->failed.assign((size_t)sl->count, 0);
+    sl->load_error.assign((size_t)sl->count, std::string());
+    sl->psize.assign((size_t)(sl->count * nin), PageSize{});
     sl->last_first = first;
     sl->last_count = sl->count;
     if (run.dsrc) {
@@ -378,9 +396,11 @@ struct SlotLoop {
     for (int j = 0; j < nin; j++) {
       uint8_t* dst = sl->hin.as() + ((int64_t)s * nin + j) * r->in_page_stride;
       const size_t q = (size_t)(s * nin + j);
-      if (!load_page(r, dc.device, run.src, sl->first + s, j, dst, &sl->jpg[q], &sl->tif[q])) {
+      if (!load_page(r, dc.device, run.src, sl->first + s, j, dst, &sl->jpg[q], &sl->tif[q], &sl->psize[q])) {
         sl->jpg[q].on = sl->tif[q].on = false;
+        sl->psize[q] = PageSize{};  // the blank page below is of the geometry's size
         sl->failed[(size_t)s] |= 4;
+        if (uphip_last_error() && sl->load_error[(size_t)s].empty()) sl->load_error[(size_t)s] = uphip_last_error();
         uphip_clear_error();
         // the slot still runs: a blank (white) page, cheap and
         // deterministic, instead of stale staging bytes
@@ -401,12 +421,12 @@ struct SlotLoop {
     bool ok;
     if (run.dsrc) {
       const size_t bytes = (size_t)((npages - 1) * src->page_stride + run.in_extent);
-      ok = UPH_HIP(hipMemcpyAsync(sl->din.as(), src->base + sl->first * nin * src->page_stride, bytes,
+      ok = place_pages(r, sl, 0) && UPH_HIP(hipMemcpyAsync(sl->din.as(), src->base + sl->first * nin * src->page_stride, bytes,
                                   hipMemcpyHostToDevice, (hipStream_t)uphip_batch_stream(sl->b))) &&
            uphip_batch_run_device(sl->b, sl->count, sl->din.as(), src->linesize, src->page_stride) == 0;
     } else {
-      ok = upload_staging(r, sl, npages) && jpeg_submit(sl, npages) && tiff_submit(sl, npages) &&
-           uphip_batch_run(sl->b, sl->count) == 0;
+      ok = place_pages(r, sl, npages) && upload_staging(r, sl, npages) && jpeg_submit(sl, npages) &&
+           tiff_submit(sl, npages) && uphip_batch_run(sl->b, sl->count) == 0;
     }
     const PackedCodec* pc = packed_codec(sink, r->out_fmt);
     if (!ok || (pc && pc->encode(sl->b, sink) != 0)) return fail_chunk(k, "run failed");
@@ -552,6 +572,7 @@ UphipRunner* uphip_runner_create(const UphipOptions* options, const UphipBatchGe
   UphipRunner* r = new UphipRunner();
   r->opts = *options;
   r->geo = *geometry;
+  r->fixed_sheet = options->sheet_size.width != -1 && options->sheet_size.height != -1 && options->pre_rotate == 0;
   r->cfg = *config;
   r->oc = options->output_count < 1 ? 1 : options->output_count;
   if (r->geo.capacity <= 0) r->geo.capacity = auto_capacity(*options, *geometry);
@@ -731,7 +752,8 @@ int uphip_runner_run_device(UphipRunner* r, const UphipDevicePages* shards, int3
         const int32_t n = (int32_t)std::min<int64_t>(S, sh.count - first);
         const size_t k = idle_slot();
         Slot& sl = dc.slots[k];
-        if (uphip_batch_run_device(sl.b, n, (const uint8_t*)sh.pages + first * nin * sh.page_stride,
+        if (!place_pages(r, &sl, 0) ||
+            uphip_batch_run_device(sl.b, n, (const uint8_t*)sh.pages + first * nin * sh.page_stride,
                                    sh.pitch, sh.page_stride) != 0) {
           if (dc.error.empty()) dc.error = uphip_last_error() ? uphip_last_error() : "run failed";
           uphip_clear_error();

@@ -27,19 +27,34 @@ int mem_load(const UphipSource* s, int64_t idx, void* dst, int64_t linesize,
   return 0;
 }
 
-int pnm_load(const UphipSource* s, int64_t idx, void* dst, int64_t linesize,
-             const UphipPnmInfo& geo) {
-  if (idx < 0 || idx >= (int64_t)s->paths.size())
-    return fail("source_pnm: page %lld out of range", (long long)idx), -1;
-  return uphip_image_read(s->paths[(size_t)idx].c_str(), dst, linesize, &geo);
+// A page the runner takes, or the error that names it: of the runner's
+// geometry, or, with a fixed sheet (sheet_size fully set, no pre_rotate), of
+// its format and at most its size.  *size: the page's.
+bool same_geometry(const UphipRunner* r, const UphipPnmInfo& g, const char* kind, const char* name,
+                   PageSize* size) {
+  const bool fmt = g.format == r->geo.page_format;
+  *size = PageSize{g.width, g.height};
+  if (fmt && g.width == r->geo.page_width && g.height == r->geo.page_height) return true;
+  if (r->fixed_sheet) {
+    if (fmt && g.width > 0 && g.height > 0 && g.width <= r->geo.page_width && g.height <= r->geo.page_height)
+      return true;
+    return fail("%s: %s is %dx%d format %d, the runner takes format %d up to the maximum %dx%d", kind, name,
+                g.width, g.height, g.format, r->geo.page_format, r->geo.page_width, r->geo.page_height);
+  }
+  return fail("%s: %s is %dx%d format %d, expected %dx%d format %d (a fully set sheet_size, without "
+              "pre_rotate, admits pages of other sizes up to the geometry's)",
+              kind, name, g.width, g.height, g.format, r->geo.page_width, r->geo.page_height,
+              r->geo.page_format);
 }
 
-// A page of the runner's geometry, or the error that names it.
-bool same_geometry(const UphipRunner* r, const UphipPnmInfo& g, const char* kind, const char* name) {
-  if (g.width == r->geo.page_width && g.height == r->geo.page_height && g.format == r->geo.page_format)
-    return true;
-  return fail("%s: %s is %dx%d format %d, expected %dx%d format %d", kind, name, g.width, g.height, g.format,
-              r->geo.page_width, r->geo.page_height, r->geo.page_format);
+int pnm_load(const UphipRunner* r, const UphipSource* s, int64_t idx, void* dst, int64_t linesize,
+             PageSize* size) {
+  if (idx < 0 || idx >= (int64_t)s->paths.size())
+    return fail("source_pnm: page %lld out of range", (long long)idx), -1;
+  const char* path = s->paths[(size_t)idx].c_str();
+  UphipPnmInfo g{0, 0, 0};
+  if (uphip_image_probe(path, &g) != 0 || !same_geometry(r, g, "source_pnm", path, size)) return -1;
+  return uphip_image_read(path, dst, linesize, &g);
 }
 
 bool is_jpeg_file(const std::string& path) {
@@ -53,12 +68,12 @@ bool is_jpeg_file(const std::string& path) {
 
 // The host half of a JPEG page into the slot's pinned buffer `jp`.
 bool jpeg_load_mem(UphipRunner* r, int device, const uint8_t* data, size_t size, const char* name,
-                   JpegPage* jp) {
+                   JpegPage* jp, PageSize* ps) {
   thread_local JdecStreamHost S;
   // the frame header first: a file of the wrong geometry (or a crafted one
   // claiming a huge frame) is refused before anything is sized from it
   UphipPnmInfo info{0, 0, 0};
-  if (!jpeg_probe_mem(data, size, name, &info) || !same_geometry(r, info, "jpeg", name)) return false;
+  if (!jpeg_probe_mem(data, size, name, &info) || !same_geometry(r, info, "jpeg", name, ps)) return false;
   // a one-scan sequential file goes to the device as its unstuffed entropy
   // data (Huffman decoding there too); progressive / multi-scan files are
   // entropy-decoded here
@@ -94,10 +109,10 @@ bool is_j2k_file(const std::string& path) {
 // The host half of a JPEG 2000 page (headers, packet headers) into the
 // slot's pinned buffer `jp`: its code-block jobs, then their codewords.
 bool j2k_load_mem(UphipRunner* r, int device, const uint8_t* data, size_t size, const char* name,
-                  JpegPage* jp) {
+                  JpegPage* jp, PageSize* ps) {
   thread_local j2k::T1Batch tb;
   UphipPnmInfo info{0, 0, 0};
-  if (!j2k::probe(data, size, name, &info) || !same_geometry(r, info, "jp2", name)) return false;
+  if (!j2k::probe(data, size, name, &info) || !same_geometry(r, info, "jp2", name, ps)) return false;
   if (!j2k::decode_host(data, size, name, &jp->img, nullptr, &tb)) return false;
   if (uphip_set_device(device) != 0) return false;
   jp->njobs = (int32_t)tb.jobs.size();
@@ -118,17 +133,19 @@ bool j2k_load_mem(UphipRunner* r, int device, const uint8_t* data, size_t size, 
 }
 
 // A JPEG or JPEG 2000 file through its loader above.
-bool file_load(decltype(jpeg_load_mem)* load, UphipRunner* r, int device, const std::string& path, JpegPage* jp) {
+bool file_load(decltype(jpeg_load_mem)* load, UphipRunner* r, int device, const std::string& path, JpegPage* jp,
+               PageSize* ps) {
   // per pool thread, kept across pages: fresh multi-MB buffers per page would
   // page-fault (and contend on the address space) on every load
   thread_local std::vector<uint8_t> file;
-  return jpeg_read_file(path.c_str(), &file) && load(r, device, file.data(), file.size(), path.c_str(), jp);
+  return jpeg_read_file(path.c_str(), &file) && load(r, device, file.data(), file.size(), path.c_str(), jp, ps);
 }
 
 // Page `idx` of a PDF source (the decode queue of the PDF pipeline,
 // pdf_pipeline_cpu_batch.c:381-496): its image's JPEG / JPEG 2000 bytes to
 // the device decode like a file's, Flate / raw pixels decoded here.
-bool pdf_load(UphipRunner* r, int device, const UphipSource* s, int64_t idx, uint8_t* dst, JpegPage* jp) {
+bool pdf_load(UphipRunner* r, int device, const UphipSource* s, int64_t idx, uint8_t* dst, JpegPage* jp,
+              PageSize* ps) {
   if (idx < 0 || idx >= s->pdf->page_count())
     return fail("source_pdf: page %lld out of range (%d pages)", (long long)idx, s->pdf->page_count());
   thread_local pdf::PageImage im;
@@ -136,9 +153,9 @@ bool pdf_load(UphipRunner* r, int device, const UphipSource* s, int64_t idx, uin
   if (!pdf::page_geometry(*s->pdf, (int)idx, s->pdf_dpi, &im, &g)) return false;
   char name[64];
   snprintf(name, sizeof(name), "pdf page %lld", (long long)idx);
-  if (im.format == pdf::kJpeg) return jpeg_load_mem(r, device, im.data.data(), im.data.size(), name, jp);
-  if (im.format == pdf::kJp2) return j2k_load_mem(r, device, im.data.data(), im.data.size(), name, jp);
-  return same_geometry(r, g, "pdf", name) && pdf::decode_pixels(im, dst, r->in_pitch, name);
+  if (im.format == pdf::kJpeg) return jpeg_load_mem(r, device, im.data.data(), im.data.size(), name, jp, ps);
+  if (im.format == pdf::kJp2) return j2k_load_mem(r, device, im.data.data(), im.data.size(), name, jp, ps);
+  return same_geometry(r, g, "pdf", name, ps) && pdf::decode_pixels(im, dst, r->in_pitch, name);
 }
 
 size_t up256(size_t n) { return (n + 255) & ~(size_t)255; }
@@ -157,11 +174,14 @@ bool is_tiff_file(const std::string& path) {
 // source asks for the device route and the page qualifies, its strips into
 // the slot's pinned blob `tp` (tiff_dec.h).
 bool tiff_load(UphipRunner* r, int device, const tiff::Document& doc, int64_t idx, bool host_only, uint8_t* dst,
-               TiffPage* tp) {
+               TiffPage* tp, PageSize* ps) {
   const tiff::Page* p = tiff::page(doc, idx);
   if (!p) return false;
   // the geometry first: nothing is sized from a page of another shape
-  if (!same_geometry(r, UphipPnmInfo{p->width, p->height, p->format}, "tiff", doc.name.c_str())) return false;
+  char name[24];
+  snprintf(name, sizeof(name), " page %lld", (long long)idx);
+  if (!same_geometry(r, UphipPnmInfo{p->width, p->height, p->format}, "tiff", (doc.name + name).c_str(), ps))
+    return false;
   if (host_only || !tiff::device_route(*p)) return tiff::decode_host(doc, *p, dst, r->in_pitch);
   if (uphip_set_device(device) != 0) return false;
   const size_t need = tiff::blob_bytes(*p);
@@ -182,23 +202,43 @@ constexpr int kJ2kSubBatch = 16;  // pages coded per k_j2k_t1enc launch (bounds 
 }  // namespace
 
 bool load_page(UphipRunner* r, int device, const UphipSource* s, int64_t job, int32_t j,
-               uint8_t* dst, JpegPage* jp, TiffPage* tp) {
+               uint8_t* dst, JpegPage* jp, TiffPage* tp, PageSize* ps) {
   const UphipPnmInfo geo{r->geo.page_width, r->geo.page_height, r->geo.page_format};
   const int64_t idx = job * r->opts.input_count + j;
+  *ps = PageSize{geo.width, geo.height};  // callback and memory sources carry no size of their own
   if (s->load) return s->load(s->user, job, j, dst, r->in_pitch) == 0;
   if (s->base) return mem_load(s, idx, dst, r->in_pitch, geo) == 0;
-  if (s->pdf) return pdf_load(r, device, s, idx, dst, jp);
-  if (s->tiff) return tiff_load(r, device, *s->tiff, idx, !(s->tiff_flags & UPHIP_TIFF_DEVICE_DECODE), dst, tp);
+  if (s->pdf) return pdf_load(r, device, s, idx, dst, jp, ps);
+  if (s->tiff) return tiff_load(r, device, *s->tiff, idx, !(s->tiff_flags & UPHIP_TIFF_DEVICE_DECODE), dst, tp, ps);
   if (idx >= 0 && idx < (int64_t)s->paths.size()) {
     const std::string& path = s->paths[(size_t)idx];
-    if (is_jpeg_file(path)) return file_load(jpeg_load_mem, r, device, path, jp);
-    if (is_j2k_file(path)) return file_load(j2k_load_mem, r, device, path, jp);
+    if (is_jpeg_file(path)) return file_load(jpeg_load_mem, r, device, path, jp, ps);
+    if (is_j2k_file(path)) return file_load(j2k_load_mem, r, device, path, jp, ps);
     if (is_tiff_file(path)) {
       tiff::Document doc;
-      return tiff::open_file(path.c_str(), &doc) && tiff_load(r, device, doc, 0, true, dst, tp);
+      return tiff::open_file(path.c_str(), &doc) && tiff_load(r, device, doc, 0, true, dst, tp, ps);
     }
   }
-  return pnm_load(s, idx, dst, r->in_pitch, geo) == 0;
+  return pnm_load(r, s, idx, dst, r->in_pitch, ps) == 0;
+}
+
+bool source_page_info(const UphipSource* s, int64_t idx, UphipPnmInfo* g, std::string* name) {
+  char buf[32];
+  snprintf(buf, sizeof(buf), " page %lld", (long long)idx);
+  if (s->pdf) {
+    thread_local pdf::PageImage im;
+    *name = "pdf" + std::string(buf);
+    return pdf::page_geometry(*s->pdf, (int)idx, s->pdf_dpi, &im, g);
+  }
+  if (s->tiff) {
+    const tiff::Page* p = tiff::page(*s->tiff, idx);
+    *name = s->tiff->name + buf;
+    if (p) *g = UphipPnmInfo{p->width, p->height, p->format};
+    return p != nullptr;
+  }
+  if (idx < 0 || idx >= (int64_t)s->paths.size()) return fail("source: page %lld out of range", (long long)idx);
+  *name = s->paths[(size_t)idx];
+  return uphip_image_probe(name->c_str(), g) == 0;
 }
 
 // Queue the H2D copy of the slot's staged pages, skipping the JPEG pages (their

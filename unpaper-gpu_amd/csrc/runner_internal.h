@@ -147,8 +147,14 @@ struct TiffPage {
   bool lzw = false;
 };
 
+struct PageSize {
+  int32_t w = 0, h = 0;
+};
+
 struct Slot {
   std::vector<JpegPage> jpg;     // per page of the chunk (sheet * input_count + page)
+  std::vector<PageSize> psize;   // likewise: each page's own size (a fixed-sheet run places by it)
+  std::vector<std::string> load_error;  // per sheet of the chunk: why its page did not load
   std::vector<TiffPage> tif;     // likewise
   Buffer dtif{Buffer::Device};   // the chunk's TIFF blobs, then its jobs and page records
   Buffer htif{Buffer::Pinned};   // the jobs and page records, offsets made chunk-wide
@@ -230,6 +236,9 @@ struct UphipRunner {
   int64_t in_pitch = 0, in_page_stride = 0;   // batch input slot layout (= staging layout)
   int64_t out_linesize = 0, out_sheet_stride = 0;
   bool staged = false;  // pinned staging allocated
+  // sheet_size fully set and no pre_rotate: geo's page size is the maximum, a
+  // page of the format and at most that size is centred in the sheet
+  bool fixed_sheet = false;
   int64_t batch_bytes = 0;  // device memory of one batch
   UphipRunnerStats stats{};
 };
@@ -259,7 +268,9 @@ bool sink_write(const UphipSink* k, int64_t idx, const uint8_t* p, size_t n, int
 
 // runner_decode.cpp
 bool load_page(UphipRunner* r, int device, const UphipSource* s, int64_t job, int32_t j, uint8_t* dst,
-               JpegPage* jp, TiffPage* tp);
+               JpegPage* jp, TiffPage* tp, PageSize* ps);
+// page idx of a PNM-list, TIFF or PDF source from its header, and a name for it
+bool source_page_info(const UphipSource* s, int64_t idx, UphipPnmInfo* g, std::string* name);
 bool upload_staging(UphipRunner* r, Slot* sl, int npages);
 bool jpeg_submit(Slot* sl, int npages);
 bool tiff_submit(Slot* sl, int npages);

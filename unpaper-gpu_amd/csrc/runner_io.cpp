@@ -174,6 +174,28 @@ int64_t uphip_source_page_count(UphipSource* s) {
   return fail("source_page_count: a callback source has no page count"), -1;
 }
 
+int uphip_source_max_geometry(UphipSource* s, UphipPnmInfo* info) {
+  if (!s || !info) return fail("source_max_geometry: null argument"), -1;
+  if (s->load || s->base)
+    return fail("source_max_geometry: callback and memory sources carry no page sizes"), -1;
+  const int64_t n = uphip_source_page_count(s);
+  if (n <= 0) return -1;
+  UphipPnmInfo m{0, 0, 0};
+  for (int64_t i = 0; i < n; i++) {
+    UphipPnmInfo g{0, 0, 0};
+    std::string name;
+    if (!source_page_info(s, i, &g, &name)) return -1;
+    if (i == 0) m.format = g.format;
+    if (g.format != m.format)
+      return fail("source_max_geometry: %s is of format %d, the pages before it of format %d (one run takes "
+                  "one page format)", name.c_str(), g.format, m.format), -1;
+    m.width = std::max(m.width, g.width);
+    m.height = std::max(m.height, g.height);
+  }
+  *info = m;
+  return 0;
+}
+
 void uphip_source_destroy(UphipSource* s) { delete s; }
 
 UphipSink* uphip_sink_callback(UphipStoreFn store, void* user) {

@@ -80,6 +80,7 @@ EXPORTED = [
     "uphip_tiff_writer_finish", "uphip_tiff_writer_close", "uphip_batch_encode_tiff_async",
     "uphip_batch_tiff_sizes", "uphip_batch_tiff_download_async", "uphip_sink_tiff",
     "uphip_sink_tiff_multipage",
+    "uphip_batch_set_page_size", "uphip_batch_decode_route", "uphip_source_max_geometry",
 ]
 
 
@@ -157,6 +158,9 @@ def load_library(path=LIB_PATH):
                                               C.POINTER(C.c_int64)]),
         "uphip_batch_input_ptr": (C.c_void_p, [C.c_void_p, C.c_int32, C.POINTER(C.c_int64)]),
         "uphip_batch_set_input": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64]),
+        "uphip_batch_set_page_size": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
+        "uphip_batch_decode_route": (C.c_int32, [C.c_void_p]),
+        "uphip_source_max_geometry": (C.c_int, [C.c_void_p, C.POINTER(A.PnmInfo)]),
         "uphip_batch_run_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64,
                                              C.c_int64]),
         "uphip_batch_run": (C.c_int, [C.c_void_p, C.c_int32]),

@@ -65,8 +65,31 @@ class Batch:
             self.set_timing(True)
         self.out_width, self.out_height, self.out_format = w.value, h.value, f.value
 
-    def set_input(self, sheet, page_index, h: HostImage):
+    def set_page_size(self, sheet, page_index, width, height):
+        """The page in this input slot is width x height, at most the batch's
+        page size; (0, 0) puts it back (uphip_batch_set_page_size: needs a
+        fully set sheet_size and no pre_rotate)."""
         slot = sheet * self.options.input_count + page_index
+        rc = self.lib.uphip_batch_set_page_size(self.handle, slot, width, height)
+        _check(self.lib)
+        if rc != 0:
+            raise UnpaperHipError("batch_set_page_size failed")
+        self._sized = True
+
+    def decode_route(self):
+        """The decode of the last run: 0 fill + copy, 1 k_decode_gray,
+        2 k_decode_gray_fit; -1 before any run."""
+        return self.lib.uphip_batch_decode_route(self.handle)
+
+    def set_input(self, sheet, page_index, h: HostImage):
+        """Upload a page; one smaller than the batch's page size sets the
+        slot's size first (a later full-size page sets it back)."""
+        slot = sheet * self.options.input_count + page_index
+        full = (h.width, h.height) == (self.geometry.page_width, self.geometry.page_height)
+        if not full:
+            self.set_page_size(sheet, page_index, h.width, h.height)
+        elif getattr(self, "_sized", False):
+            self.set_page_size(sheet, page_index, 0, 0)
         arr = np.ascontiguousarray(h.data)
         # the copy is asynchronous on the batch stream: the source must live
         # until the stream has passed it (released by wait())
@@ -327,6 +350,7 @@ class Runner:
             raise UnpaperHipError("no such batch")
         b = Batch.__new__(Batch)
         b.lib, b.options, b.capacity, b.handle = self.lib, self.options, self.geometry.capacity, h
+        b.geometry = self.geometry
         b.out_width, b.out_height, b.out_format = self.out_width, self.out_height, self.out_format
         b.close = lambda: None
         return b
@@ -409,6 +433,20 @@ def source_pnm(paths):
     h = L.uphip_source_pnm(arr, len(paths))
     _check(L)
     return _Handle(h, L.uphip_source_destroy, (arr,))
+
+
+def source_max_geometry(src):
+    """(width, height, format): the largest width and height and the common
+    format over the pages of a PNM-list, TIFF or PDF source
+    (uphip_source_max_geometry): the geometry of a Runner whose options have
+    a fully set sheet_size."""
+    L = load_library()
+    info = A.PnmInfo()
+    rc = L.uphip_source_max_geometry(src.handle, C.byref(info))
+    _check(L)
+    if rc != 0:
+        raise UnpaperHipError("source_max_geometry failed")
+    return info.width, info.height, info.format
 
 
 def source_pdf(path, dpi=0):
