@@ -445,6 +445,13 @@ typedef struct {
 } UphipSheetReport;
 int uphip_batch_get_report(UphipBatch *batch, int32_t sheet,
                            UphipSheetReport *report);
+/* The masks of a sheet as arrays of the caller's size: returns the sheet's
+ * mask_count, or -1, and fills min(mask_count, capacity) entries of `masks`
+ * (the last detection's, the centring stage's unless it is disabled) and of
+ * `rotations` (what the deskew stage found for that index, 0 where none).
+ * Either array may be NULL.  Waits for the batch stream. */
+int32_t uphip_batch_get_masks(UphipBatch *batch, int32_t sheet, UphipRectangle *masks,
+                              float *rotations, int32_t capacity);
 /* Asynchronous staging for host-fed pipelines (the pinned, double-buffered
  * staging of src/pipeline/image_pipeline.c:226-376; uphip_runner_* drives
  * these).  All work is queued on the batch stream; with pinned host buffers

@@ -252,6 +252,23 @@ int uphip_batch_get_report(UphipBatch* b, int32_t sheet, UphipSheetReport* r) {
   return 0;
 }
 
+int32_t uphip_batch_get_masks(UphipBatch* b, int32_t sheet, UphipRectangle* masks, float* rotations,
+                              int32_t capacity) {
+  if (!b || sheet < 0 || sheet >= b->cap || capacity < 0)
+    return fail("batch_get_masks: bad arguments"), -1;
+  SheetCtl c;
+  hipSetDevice(b->device);
+  hipStreamSynchronize(b->st);
+  if (!UPH_HIP(hipMemcpy(&c, &b->ctl[sheet], sizeof(c), hipMemcpyDeviceToHost))) return -1;
+  const int32_t n = imin(imin(c.mask_count, capacity), UPHIP_MAX_POINTS);
+  for (int32_t i = 0; i < n; i++) {
+    if (masks) masks[i] = c.masks[i];
+    // SheetCtl keeps a rotation per mask the batch deskews (UPHIP_MAX_PAGES)
+    if (rotations) rotations[i] = i < UPHIP_MAX_PAGES ? c.rotation[i] : 0.0f;
+  }
+  return c.mask_count;
+}
+
 void* uphip_batch_stream(UphipBatch* b) { return b ? (void*)b->st : nullptr; }
 
 int uphip_batch_output_pitch(UphipBatch* b, int64_t* pitch) {

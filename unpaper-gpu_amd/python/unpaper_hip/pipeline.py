@@ -265,6 +265,19 @@ class Batch:
         self.lib.uphip_batch_get_report(self.handle, sheet, C.byref(r))
         return r
 
+    def masks(self, sheet, capacity=A.MAX_POINTS):
+        """(mask_count, masks, rotations) of a sheet: the masks of the last
+        detection and the rotation the deskew found for each
+        (uphip_batch_get_masks)."""
+        m = (A.Rectangle * max(capacity, 1))()
+        r = (C.c_float * max(capacity, 1))()
+        n = self.lib.uphip_batch_get_masks(self.handle, sheet, m, r, capacity)
+        if n < 0:
+            _check(self.lib)
+            raise UnpaperHipError("batch_get_masks failed")
+        k = min(n, capacity)
+        return n, [m[i] for i in range(k)], [r[i] for i in range(k)]
+
     def set_timing(self, enable=True):
         """Record per-stage HIP events on every run (uphip_batch_set_timing)."""
         self.lib.uphip_batch_set_timing(self.handle, 1 if enable else 0)
