@@ -238,6 +238,57 @@ int32_t uphip_detect_rotation_peaks(UphipImage image, UphipRectangle mask,
 void uphip_deskew(UphipImage source, UphipRectangle mask, float radians,
                   UphipInterpolation interpolate_type);
 
+/* The batch's move launchers on one GRAY8 image, with the arguments a batch
+ * derives from its detections given directly: center_mask (masks.c:222-249)
+ * as `center`, apply_masks + align_mask (masks.c:265-322) as `mask` + `align`.
+ * A step is the raw move: `area` as given, its target's top-left, the
+ * background wiped in, and `active` (0: the identity, no pass). */
+typedef struct {
+  UphipRectangle area;
+  int32_t tx, ty;
+  UphipPixel bg;
+  int32_t active;
+} UphipMoveStep;
+
+typedef enum {
+  UPHIP_MOVE_PLAIN = 0,    /* center, plain move                      -> image            */
+  UPHIP_MOVE_COUNT = 1,    /* center, counting its result's rows      -> image, rows      */
+  UPHIP_MOVE_DRY = 2,      /* center, counting only (ranges, only)    -> rows             */
+  UPHIP_MOVE_MASKED = 3,   /* mask + align in one pass; an inactive
+                              align masks the image in place          -> image            */
+  UPHIP_MOVE_TWO_PASS = 4, /* COUNT, then MASKED on its result        -> image, rows      */
+  UPHIP_MOVE_CHAIN = 5,    /* DRY, then center + mask + align as one
+                              gather from the uncentred image         -> image, rows      */
+} UphipMoveRoute;
+
+/* rows_out[y] of a row no counting pass reached */
+#define UPHIP_MOVE_ROW_UNWRITTEN 0xFFFFFFFFu
+
+typedef struct {
+  int32_t route;            /* UphipMoveRoute */
+  UphipMoveStep center, align;
+  int32_t mask_count;       /* 0 (apply_masks with no mask: nothing) or 1 */
+  UphipRectangle mask;      /* as given (may be inverted) */
+  UphipPixel mask_color;
+  /* counting: rows_out[y] = pixels <= thr of the centred image's row y in
+   * columns [rx0, rx1] */
+  int32_t rx0, rx1;
+  uint8_t thr;
+  /* DRY, CHAIN: rows [ya0, ya1) and [yb0, yb1) only; all four 0 = every row */
+  int32_t ya0, ya1, yb0, yb1;
+  /* DRY, CHAIN: < 0 no `only` list; else the image's entry of one (0: the
+   * counting pass leaves the image out) */
+  int32_t only;
+} UphipMoveProbe;
+
+/* Runs `p->route` on `image` (replaced by the result where the route writes
+ * one) and, for the counting routes, fills rows_out[0 .. height); DRY and
+ * CHAIN prefill it with UPHIP_MOVE_ROW_UNWRITTEN.  Returns 0, or -1 with the
+ * error set: bad arguments, or a launcher refused (an image that is not
+ * GRAY8, row ranges without a dry pass, a dry pass with a mask).  Not a
+ * backend entry. */
+int uphip_move_probe(UphipImage image, const UphipMoveProbe *p, uint32_t *rows_out);
+
 /* The vtable itself, field-for-field ImageBackend (backend.h:19-57). */
 typedef struct {
   const char *name;

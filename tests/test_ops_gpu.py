@@ -241,6 +241,47 @@ def test_align_mask(hip, oracle, fmt, inside, outside, align):
     assert_same(d.to_host(), h)
 
 
+def _align_geometries():
+    """The align moves of the move suite's table (tests/move_cases.py) at
+    97 x 61, 97 x 100 and 48 x 33: every realignment, breakpoint, row and degenerate
+    class of a single move."""
+    import move_cases as MC
+    return [c for c in MC.all_cases() if c.route == MC.MASKED and c.align is not None and
+            (c.W, c.H) in ((97, 61), (97, 100), (48, 33))]
+
+
+@pytest.mark.parametrize("fmt", [A.FMT_RGB24, A.FMT_Y400A, A.FMT_GRAY8])
+def test_align_mask_geometries(hip, oracle, fmt):
+    """uphip_align_mask over the move table's geometries on pages of random
+    bytes: k_move_rect_rgb's dword path (the byte shift 3 (A.x0 - tx), its
+    alignbyte, dwords straddling a class change at xb / 3), k_move_rect for
+    Y400A, and k_move_rect_g16 as the op launches it."""
+    from unpaper_hip.hostimage import HostImage
+    cases = _align_geometries()
+    claimed = {k for c in cases for k in c.classes}
+    assert {"masked.realign.%d.%s" % (r, o) for r in range(16) for o in ("on", "off")} <= claimed
+    assert {c.family for c in cases} >= {"realignment", "breakpoints", "rows", "degenerate"}
+    shape = {A.FMT_RGB24: (3,), A.FMT_Y400A: (2,), A.FMT_GRAY8: ()}[fmt]
+    bad = []
+    for c in cases:
+        rng = np.random.default_rng(c.seed)
+        arr = rng.integers(0, 256, size=(c.H, c.W) + shape, dtype=np.uint8)
+        h = HostImage.from_array(arr, fmt, background=(c.bg1, c.bg2, c.mcol))
+        p = A.MaskAlignmentParameters()
+        p.alignment = A.Edges(*[bool(v) for v in c.align["alignment"]])
+        p.margin = A.Delta(*c.align["margin"])
+        d = hip.upload(h)
+        hip.align_mask(d, A.rect(*c.align["inside"]), A.rect(*c.align["outside"]), p)
+        oracle.align_mask(h, A.rect(*c.align["inside"]), A.rect(*c.align["outside"]), p)
+        got = d.to_host()
+        d.close()
+        diff = np.argwhere(got.payload() != h.payload())
+        if len(diff):
+            bad.append("%s: %d bytes differ, first at row %d byte %d" % (
+                c.id, len(diff), diff[0][0], diff[0][1]))
+    assert not bad, "\n".join(bad[:40])
+
+
 @pytest.mark.parametrize("fmt", FORMATS)
 @pytest.mark.parametrize("interp", [A.INTERP_NN, A.INTERP_LINEAR, A.INTERP_CUBIC])
 @pytest.mark.parametrize("deg", [2.0, -0.7, 4.9])

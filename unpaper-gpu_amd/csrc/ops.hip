@@ -437,6 +437,136 @@ void uphip_align_mask(UphipImage image0, const UphipRectangle inside_area,
   mp.finish();
 }
 
+static MoveArgs move_args_of(const UphipMoveStep& m) {
+  return MoveArgs{to_rect(m.area), m.tx, m.ty, {m.bg.r, m.bg.g, m.bg.b}, m.active ? 1 : 0};
+}
+
+int uphip_move_probe(UphipImage image, const UphipMoveProbe* p, uint32_t* rows_out) {
+  // the batch's post stage moves (pipeline_run.hip: the centring loop and
+  // border_all) on one frame, through the same launchers
+  if (!p) return fail("move_probe: no record"), -1;
+  if (!ok_image(image, "move_probe")) return -1;
+  const int route = p->route;
+  if (route < UPHIP_MOVE_PLAIN || route > UPHIP_MOVE_CHAIN)
+    return fail("move_probe: unknown route %d", route), -1;
+  const bool counts = route != UPHIP_MOVE_PLAIN && route != UPHIP_MOVE_MASKED;
+  const bool dry = route == UPHIP_MOVE_DRY || route == UPHIP_MOVE_CHAIN;
+  if (counts && !rows_out) return fail("move_probe: the route counts rows; no rows_out"), -1;
+  if (p->mask_count < 0 || p->mask_count > 1)
+    return fail("move_probe: %d masks (0 or 1)", p->mask_count), -1;
+  UphipFrame* f = image.frame;
+  const int32_t H = f->height;
+  if (p->ya0 < 0 || p->ya1 > H || p->yb0 < 0 || p->yb1 > H)
+    return fail("move_probe: row ranges outside [0, %d]", H), -1;
+  // the kernels count whole vectors: the row padding past the width is not
+  // theirs to count (a batch counts the clipped outside rectangle's columns)
+  if (counts && (p->rx0 < 0 || p->rx1 >= f->width))
+    return fail("move_probe: counted columns outside [0, %d)", f->width), -1;
+  hipStream_t st = current_stream();
+  const MoveArgs hc = move_args_of(p->center), ha = move_args_of(p->align);
+  MaskArgs hm{};
+  hm.n = p->mask_count;
+  hm.color[0] = p->mask_color.r;
+  hm.color[1] = p->mask_color.g;
+  hm.color[2] = p->mask_color.b;
+  hm.m[0] = to_rect(p->mask);
+  const int32_t honly = p->only;
+  MoveArgs* dc = stage_args(&hc, 1, st);
+  MoveArgs* da = stage_args(&ha, 1, st);
+  MaskArgs* dm = stage_args(&hm, 1, st);
+  const int32_t* donly = honly >= 0 ? stage_args(&honly, 1, st) : nullptr;
+  if (!dc || !da || !dm || (honly >= 0 && !donly)) return -1;
+  uint32_t* rows = nullptr;
+  if (counts) {
+    if (!UPH_HIP(hipMalloc(&rows, sizeof(uint32_t) * H))) return -1;
+    UPH_HIP(hipMemsetAsync(rows, dry ? 0xFF : 0, sizeof(uint32_t) * H, st));
+  }
+  // `cur` holds the pixels so far; a pass that writes a plane makes it `cur`
+  UphipFrame* cur = f;
+  auto step_to = [&](UphipFrame* n) {
+    if (cur != f) frame_free(cur);
+    cur = n;
+  };
+  bool ok = true;
+  const char* refused = nullptr;
+  MoveExtra xc{};  // the centring move's counting pass
+  xc.rows = rows;
+  xc.rows_stride = H;
+  xc.rx0 = p->rx0;
+  xc.rx1 = p->rx1;
+  xc.thr = p->thr;
+  xc.dry = dry;
+  xc.ya0 = p->ya0;
+  xc.ya1 = p->ya1;
+  xc.yb0 = p->yb0;
+  xc.yb1 = p->yb1;
+  xc.only = dry ? donly : nullptr;
+  if (route == UPHIP_MOVE_DRY && p->mask_count > 0) xc.masks = dm;
+  if (route == UPHIP_MOVE_PLAIN) {
+    if (hc.active) {
+      UphipFrame* n = frame_alloc(f->width, f->height, f->format);
+      ok = n != nullptr;
+      if (ok) {
+        launch_move_rect(ref_of(cur), ref_of(n), dc, 1, st);
+        step_to(n);
+      }
+    }
+  } else if (counts) {
+    // a dry pass writes nothing: its destination is the image itself, so a
+    // byte it wrote would show
+    UphipFrame* n = dry ? cur : frame_alloc(f->width, f->height, f->format);
+    ok = n != nullptr;
+    if (ok && !launch_move_rect_fused(ref_of(cur), ref_of(n), dc, xc, 1, st)) {
+      ok = false;
+      refused = "the counting pass";
+    }
+    if (n && !dry) {
+      if (ok && hc.active) step_to(n);  // an inactive move counts the image as it is
+      else frame_free(n);
+    }
+  }
+  if (ok && (route == UPHIP_MOVE_MASKED || route == UPHIP_MOVE_TWO_PASS)) {
+    UphipFrame* n = frame_alloc(f->width, f->height, f->format);
+    MoveExtra xm{};
+    xm.masks = dm;
+    ok = n != nullptr;
+    if (ok && !launch_move_rect_fused(ref_of(cur), ref_of(n), da, xm, 1, st)) {
+      ok = false;
+      refused = "the masked move";
+    }
+    if (n) {
+      if (ok && ha.active) step_to(n);  // an inactive move masks `cur` in place
+      else frame_free(n);
+    }
+  } else if (ok && route == UPHIP_MOVE_CHAIN) {
+    UphipFrame* n = frame_alloc(f->width, f->height, f->format);
+    ok = n != nullptr;
+    if (ok && !launch_move_chain(ref_of(cur), ref_of(n), dc, dm, da, 1, st)) {
+      ok = false;
+      refused = "the chained move";
+    }
+    if (n) {
+      if (ok) step_to(n);
+      else frame_free(n);
+    }
+  }
+  arg_fence(st);
+  if (ok && counts)
+    ok = UPH_HIP(hipMemcpyAsync(rows_out, rows, sizeof(uint32_t) * H, hipMemcpyDeviceToHost, st)) &&
+         UPH_HIP(hipStreamSynchronize(st));
+  if (rows) {
+    hipStreamSynchronize(st);
+    hipFree(rows);
+  }
+  if (refused) fail("move_probe: the launcher refused %s", refused);
+  if (!ok) {
+    if (cur != f) frame_free(cur);
+    return -1;
+  }
+  if (cur != f) adopt_storage(f, cur);
+  return 0;
+}
+
 UphipBorder uphip_detect_border(UphipImage image0, UphipBorderScanParameters params,
                                 const UphipRectangle outside_mask) {
   // detect_border_cpu / detect_border_edge, masks.c:410-488

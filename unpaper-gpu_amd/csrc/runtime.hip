@@ -371,6 +371,7 @@ size_t uphip_abi_sizeof(const char* name) {
   S(UphipBorderScanParameters) S(UphipDeskewParameters) S(UphipOptions)
   S(UphipSheetReport) S(UphipBatchGeometry) S(UphipImage) S(UphipInterpolation) S(UphipLayout)
   S(UphipRunnerConfig) S(UphipDevicePages) S(UphipRunnerStats) S(UphipPnmInfo)
+  S(UphipMoveStep) S(UphipMoveProbe)
 #undef S
   return 0;
 }

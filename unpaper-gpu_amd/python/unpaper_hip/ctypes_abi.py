@@ -259,6 +259,34 @@ class BatchGeometry(C.Structure):
     ]
 
 
+MOVE_PLAIN, MOVE_COUNT, MOVE_DRY, MOVE_MASKED, MOVE_TWO_PASS, MOVE_CHAIN = range(6)
+MOVE_ROW_UNWRITTEN = 0xFFFFFFFF
+
+
+class MoveStep(C.Structure):
+    _fields_ = [("area", Rectangle), ("tx", C.c_int32), ("ty", C.c_int32), ("bg", Pixel),
+                ("active", C.c_int32)]
+
+
+class MoveProbe(C.Structure):
+    _fields_ = [
+        ("route", C.c_int32),
+        ("center", MoveStep),
+        ("align", MoveStep),
+        ("mask_count", C.c_int32),
+        ("mask", Rectangle),
+        ("mask_color", Pixel),
+        ("rx0", C.c_int32),
+        ("rx1", C.c_int32),
+        ("thr", C.c_uint8),
+        ("ya0", C.c_int32),
+        ("ya1", C.c_int32),
+        ("yb0", C.c_int32),
+        ("yb1", C.c_int32),
+        ("only", C.c_int32),
+    ]
+
+
 def rect(x0, y0, x1, y1):
     return Rectangle.make(x0, y0, x1, y1)
 

@@ -81,7 +81,7 @@ EXPORTED = [
     "uphip_batch_tiff_sizes", "uphip_batch_tiff_download_async", "uphip_sink_tiff",
     "uphip_sink_tiff_multipage",
     "uphip_batch_set_page_size", "uphip_batch_decode_route", "uphip_source_max_geometry",
-    "uphip_batch_get_masks",
+    "uphip_batch_get_masks", "uphip_move_probe",
 ]
 
 
@@ -138,6 +138,7 @@ def load_library(path=LIB_PATH):
         "uphip_detect_rotation_peaks": (C.c_int32, [Image, A.Rectangle, A.DeskewParameters,
                                                     C.c_void_p, C.c_int32]),
         "uphip_deskew": (None, [Image, A.Rectangle, C.c_float, C.c_int]),
+        "uphip_move_probe": (C.c_int, [Image, C.POINTER(A.MoveProbe), C.c_void_p]),
         "uphip_try_init": (C.c_int, []),
         "uphip_init_status_string": (C.c_char_p, [C.c_int]),
         "uphip_device_count": (C.c_int, []),
@@ -510,6 +511,18 @@ class Backend:
         if n < 0:
             raise UnpaperHipError("detect_rotation_peaks failed")
         return out[:n].copy()
+
+    def move_probe(self, d, probe):
+        """uphip_move_probe: the image is replaced where the route writes one;
+        returns the counting routes' rows as a uint32 array (else None)."""
+        counts = probe.route not in (A.MOVE_PLAIN, A.MOVE_MASKED)
+        rows = np.zeros(d.size[1], np.uint32) if counts else None
+        rc = self.lib.uphip_move_probe(d.img, C.byref(probe),
+                                       rows.ctypes.data if counts else None)
+        self._done()
+        if rc != 0:
+            raise UnpaperHipError("move_probe failed")
+        return rows
 
     def detect_rotation(self, d, mask, params):
         r = self.lib.uphip_detect_rotation(d.img, mask, params); self._done()
