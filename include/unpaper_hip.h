@@ -503,6 +503,13 @@ int uphip_batch_get_report(UphipBatch *batch, int32_t sheet,
  * Either array may be NULL.  Waits for the batch stream. */
 int32_t uphip_batch_get_masks(UphipBatch *batch, int32_t sheet, UphipRectangle *masks,
                               float *rotations, int32_t capacity);
+/* Not a backend entry: how the later runs of a batch with more than two
+ * mask-scan points sum their scan bars.  0 (the default): every point's sums
+ * in one launch; 1: per point and axis with the reductions a batch of one or
+ * two points uses, the parity twin and the time baseline.  Both give the same
+ * sheets.  Any other route is refused (-1); a batch of one or two points has
+ * one way only and ignores the setting. */
+int uphip_batch_set_mask_scan_route(UphipBatch *batch, int32_t route);
 /* Asynchronous staging for host-fed pipelines (the pinned, double-buffered
  * staging of src/pipeline/image_pipeline.c:226-376; uphip_runner_* drives
  * these).  All work is queued on the batch stream; with pinned host buffers

@@ -5,7 +5,7 @@ out.pdf`), on the runner's PDF source and sink.
 
     python tools/pdf_pipeline.py in.pdf out.pdf [--pdf-quality fast|high]
         [--pdf-dpi N] [--jpeg-quality Q] [--input-pages 1|2] [--output-pages 1|2]
-        [--sheet-size WxH]
+        [--sheet-size WxH] [--mask-scan-point X,Y ...]
 
 Every input page is decoded where its codec runs (JPEG / JPEG 2000 on the
 device, JBIG2 / CCITT / Flate on the load pool), the sheets go through the
@@ -17,6 +17,10 @@ the pages may be of any sizes: the runner is sized for the largest
 cropped where larger.  Without it the pages must share the first page's image
 geometry; a page that does not is left out of the output, as the reference's
 page accumulator leaves out failed pages.
+--mask-scan-point X,Y (the reference's option, repeatable up to
+UPHIP_MAX_POINTS times) gives the points the mask detection starts from, in
+sheet pixels, in place of the layout's: one mask is detected, deskewed and
+centred per point, in the order given.
 --pdf-dpi 0 (the default here) takes the page images as they are; a dpi
 applies the reference's size check (an image off the page size would need
 a rasteriser and fails).
@@ -37,7 +41,24 @@ from unpaper_hip.pipeline import (Runner, sink_pdf, source_max_geometry, source_
                                   source_pdf)
 
 
-def main():
+def point_arg(text):
+    try:
+        x, y = (int(v) for v in text.split(","))
+    except ValueError:
+        raise argparse.ArgumentTypeError("expected X,Y, got %r" % text)
+    return x, y
+
+
+def apply_mask_scan_points(opts, points):
+    """The options' mask-scan points from --mask-scan-point's list."""
+    if len(points) > A.MAX_POINTS:
+        raise ValueError("--mask-scan-point: at most %d points (got %d)" % (A.MAX_POINTS, len(points)))
+    opts.point_count = len(points)
+    for i, (x, y) in enumerate(points):
+        opts.points[i] = A.Point(x, y)
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("input")
     ap.add_argument("output")
@@ -47,9 +68,15 @@ def main():
     ap.add_argument("--input-pages", type=int, default=1, choices=(1, 2))
     ap.add_argument("--output-pages", type=int, default=1, choices=(1, 2))
     ap.add_argument("--sheet-size", metavar="WxH", help="one sheet size in pixels: admits pages of any sizes")
+    ap.add_argument("--mask-scan-point", metavar="X,Y", type=point_arg, action="append", default=[],
+                    help="a point the mask detection starts from (repeatable)")
     ap.add_argument("--sheets-per-batch", type=int, default=16)
     ap.add_argument("--streams", type=int, default=8)
-    args = ap.parse_args()
+    return ap.parse_args(argv)
+
+
+def main():
+    args = parse_args()
 
     L = load_library()
     doc = P.PdfDocument.open(args.input)
@@ -59,6 +86,7 @@ def main():
     L.uphip_options_init(C.byref(opts))
     opts.input_count = args.input_pages
     opts.output_count = args.output_pages
+    apply_mask_scan_points(opts, args.mask_scan_point)
     src = source_pdf(args.input, args.pdf_dpi)
     if args.sheet_size:
         sw, sh = (int(v) for v in args.sheet_size.lower().split("x"))

@@ -285,6 +285,163 @@ void launch_axis_reduce(const PlaneRef& ref, const AxisArgs* args, int axis, int
   }
 }
 
+// ---------------------------------------------------------------------------
+// detect_masks' bar sums of every point in one launch (more than two points).
+// A point's horizontal scan reads the column sums over the rows of its band,
+// its vertical scan the row sums over the band's columns (masks.c:54-100);
+// every (point, axis) is a job with its own W (or H) entries of the sheet's
+// sums row.  blockIdx.x runs over the column tiles of axis 0, then the row
+// tiles of axis 1; blockIdx.y is the point, blockIdx.z the sheet.  A block
+// owns its tile's entries: it reads the band only, reduces in registers and
+// across its waves in LDS (axis 0) or across a row's lanes (axis 1) and
+// stores every entry, zeros for an empty band -- no atomics, nothing to clear.
+// ---------------------------------------------------------------------------
+constexpr int kPointRowIters = 4;  // axis 1: rows a lane segment (a wave) takes in turn
+
+template <int FMT>
+__global__ void __launch_bounds__(256) k_mask_sums_points(PlaneRef ref, const PointBand* bands,
+                                                          int32_t W, int32_t H, int tiles0,
+                                                          int seg_log2, uint32_t* out,
+                                                          int64_t out_stride) {
+  const int s = blockIdx.z;
+  const int axis = (int)blockIdx.x >= tiles0 ? 1 : 0;
+  const int32_t tile = (int32_t)blockIdx.x - (axis ? tiles0 : 0);
+  const PointBand bd = bands[blockIdx.y * 2 + axis];
+  const uint8_t* base = plane_ptr(ref, s);
+  const int64_t pitch = ref.P.pitch;
+  uint32_t* o = out + (int64_t)s * out_stride + bd.sums_offset;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  __shared__ __attribute__((aligned(16))) uint32_t red[4][256];
+  if (axis == 0 && FMT == F_GRAY8) {
+    // a lane owns 4 columns (one aligned dword a row, inside the row's pitch);
+    // the waves take the band's rows in groups of 8 in turn.  The columns
+    // accumulate as 16-bit lanes of two words, flushed every 32 groups:
+    // 256 rows of <= 255.
+    static_assert(32 * 8 * 255 < 65536, "16-bit column lanes");
+    const int32_t vx = (tile * 64 + lane) * 4;
+    const uint8_t* p = base + (vx < W ? vx : 0);
+    uint32_t acc[4] = {0, 0, 0, 0};
+    int32_t y = bd.lo + w * 8;
+    while (y <= bd.hi) {
+      uint32_t a02 = 0, a13 = 0;
+      for (int g = 0; g < 32 && y <= bd.hi; g++, y += 32) {
+        uint32_t v[8];
+#pragma unroll
+        for (int k = 0; k < 8; k++)  // rows past the band re-read its last row and are not summed
+          v[k] = *reinterpret_cast<const uint32_t*>(p + (int64_t)imin(y + k, bd.hi) * pitch);
+#pragma unroll
+        for (int k = 0; k < 8; k++)
+          if (y + k <= bd.hi) {
+            a02 += v[k] & 0x00FF00FFu;
+            a13 += (v[k] >> 8) & 0x00FF00FFu;
+          }
+      }
+      acc[0] += a02 & 0xFFFFu;
+      acc[1] += a13 & 0xFFFFu;
+      acc[2] += a02 >> 16;
+      acc[3] += a13 >> 16;
+    }
+    *reinterpret_cast<uint4*>(&red[w][lane * 4]) = uint4{acc[0], acc[1], acc[2], acc[3]};
+    __syncthreads();
+    const int c = threadIdx.x;
+    const int32_t x = tile * 256 + c;
+    if (x < W) o[x] = red[0][c] + red[1][c] + red[2][c] + red[3][c];
+  } else if (axis == 0) {
+    // a lane owns a column of the block's 64, the waves every fourth row
+    const int32_t x = tile * 64 + lane;
+    const int32_t xr = x < W ? x : 0;
+    uint32_t acc = 0;
+    for (int32_t y = bd.lo + w; y <= bd.hi; y += 16) {
+#pragma unroll
+      for (int k = 0; k < 4; k++)
+        if (y + 4 * k <= bd.hi)
+          acc += measure<FMT, M_GRAY_SUM>(base + (int64_t)(y + 4 * k) * pitch, xr, 0);
+    }
+    red[w][lane] = acc;
+    __syncthreads();
+    if (w == 0 && x < W) o[x] = red[0][lane] + red[1][lane] + red[2][lane] + red[3][lane];
+  } else if (FMT == F_GRAY8) {
+    // a row is a segment of L lanes over the band's 16-byte vectors
+    // (k_rowsum_g); only the two edge vectors are masked byte by byte
+    const int L = 1 << seg_log2, sl = threadIdx.x & (L - 1), segs = 256 >> seg_log2;
+    const bool empty = bd.lo > bd.hi;
+    const int32_t a0 = bd.lo & ~15, nv = empty ? 0 : ((bd.hi | 15) - a0 + 1) >> 4;
+    for (int it = 0; it < kPointRowIters; it++) {
+      const int32_t y = (tile * kPointRowIters + it) * segs + (int32_t)(threadIdx.x >> seg_log2);
+      const bool live = y < H;
+      const uint8_t* row = base + (int64_t)(live ? y : 0) * pitch;
+      uint32_t acc = 0;
+      for (int32_t v0 = 0; v0 < nv; v0 += 4 * L) {
+        uint4 v[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+          const int32_t vi = v0 + k * L + sl;
+          v[k] = *reinterpret_cast<const uint4*>(row + a0 + 16 * (vi < nv ? vi : 0));
+        }
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+          const int32_t vi = v0 + k * L + sl;
+          if (vi >= nv) continue;
+          const int32_t c = a0 + 16 * vi;
+          const uint32_t wd[4] = {v[k].x, v[k].y, v[k].z, v[k].w};
+#pragma unroll
+          for (int j = 0; j < 4; j++) {
+            const int32_t x = c + 4 * j;
+            if (x >= bd.lo && x + 3 <= bd.hi) {
+              acc = measure_g4_full<M_GRAY_SUM>(wd[j], 0u, acc);
+            } else {
+              uint32_t keep = 0;
+#pragma unroll
+              for (int q = 0; q < 4; q++)
+                if (x + q >= bd.lo && x + q <= bd.hi) keep |= 0xFFu << (8 * q);
+              acc = measure_g4<M_GRAY_SUM>(wd[j], keep, 0u, acc);
+            }
+          }
+        }
+      }
+      for (int d = L >> 1; d > 0; d >>= 1) acc += __shfl_down(acc, d, L);
+      if (sl == 0 && live) o[y] = acc;
+    }
+  } else {
+    // a wave a row, its lanes striding over the band's columns
+    for (int it = 0; it < kPointRowIters; it++) {
+      const int32_t y = (tile * kPointRowIters + it) * 4 + w;
+      const bool live = y < H;
+      const uint8_t* row = base + (int64_t)(live ? y : 0) * pitch;
+      uint32_t acc = 0;
+      for (int32_t x = bd.lo + lane; x <= bd.hi; x += 64) acc += measure<FMT, M_GRAY_SUM>(row, x, 0);
+      for (int d = 32; d > 0; d >>= 1) acc += __shfl_down(acc, d, 64);
+      if (lane == 0 && live) o[y] = acc;
+    }
+  }
+}
+
+void launch_mask_sums_points(const PlaneRef& ref, const PointBand* bands, int npoints, int32_t W,
+                             int32_t H, int32_t band_cols, uint32_t* out, int64_t out_stride,
+                             int count, hipStream_t st) {
+  if (npoints <= 0 || count <= 0 || W <= 0 || H <= 0) return;
+  const bool gray = ref.P.fmt == F_GRAY8;
+  const int lg = gray ? rowsum_gray_lg(imin(imax(band_cols, 1), W)) : 6;
+  const int tiles0 = gray ? (W + 255) / 256 : (W + 63) / 64;
+  const int rows_per_block = (256 >> lg) * kPointRowIters;
+  const int tiles1 = (H + rows_per_block - 1) / rows_per_block;
+  const dim3 grid(tiles0 + tiles1, npoints, count);
+  switch (ref.P.fmt) {
+    case F_GRAY8:
+      hipLaunchKernelGGL((k_mask_sums_points<F_GRAY8>), grid, dim3(256), 0, st, ref, bands, W, H,
+                         tiles0, lg, out, out_stride);
+      break;
+    case F_Y400A:
+      hipLaunchKernelGGL((k_mask_sums_points<F_Y400A>), grid, dim3(256), 0, st, ref, bands, W, H,
+                         tiles0, lg, out, out_stride);
+      break;
+    default:
+      hipLaunchKernelGGL((k_mask_sums_points<F_RGB24>), grid, dim3(256), 0, st, ref, bands, W, H,
+                         tiles0, lg, out, out_stride);
+      break;
+  }
+}
+
 // Block-wide inclusive prefix sum of `v` (256 threads = 4 waves) plus a carry.
 __device__ __forceinline__ uint32_t block_prefix(uint32_t v, uint32_t carry, uint32_t* wsum) {
   uint32_t pre = v;

@@ -261,12 +261,26 @@ int32_t uphip_batch_get_masks(UphipBatch* b, int32_t sheet, UphipRectangle* mask
   hipStreamSynchronize(b->st);
   if (!UPH_HIP(hipMemcpy(&c, &b->ctl[sheet], sizeof(c), hipMemcpyDeviceToHost))) return -1;
   const int32_t n = imin(imin(c.mask_count, capacity), UPHIP_MAX_POINTS);
+  // SheetCtl keeps UPHIP_MAX_PAGES rotations; a batch of more points keeps
+  // every mask's in rot_all
+  std::vector<float> all(b->rot_all ? b->points.size() : 0);
+  if (!all.empty() && !UPH_HIP(hipMemcpy(all.data(), b->rot_all + (size_t)sheet * all.size(),
+                                         sizeof(float) * all.size(), hipMemcpyDeviceToHost)))
+    return -1;
   for (int32_t i = 0; i < n; i++) {
     if (masks) masks[i] = c.masks[i];
-    // SheetCtl keeps a rotation per mask the batch deskews (UPHIP_MAX_PAGES)
-    if (rotations) rotations[i] = i < UPHIP_MAX_PAGES ? c.rotation[i] : 0.0f;
+    if (rotations)
+      rotations[i] = (size_t)i < all.size() ? all[i] : i < UPHIP_MAX_PAGES ? c.rotation[i] : 0.0f;
   }
   return c.mask_count;
+}
+
+int uphip_batch_set_mask_scan_route(UphipBatch* b, int32_t route) {
+  if (!b) return fail("batch_set_mask_scan_route: null batch"), -1;
+  if (route != 0 && route != 1)
+    return fail("batch_set_mask_scan_route: unknown route %d (0 one launch, 1 looped)", route), -1;
+  b->mask_scan_route = route;
+  return 0;
 }
 
 void* uphip_batch_stream(UphipBatch* b) { return b ? (void*)b->st : nullptr; }

@@ -110,9 +110,12 @@ struct BatchArgs {
     const MaskArgs* border = nullptr;
   } pre;
   struct {  // detect_masks: both scans (deskew, centring) read the same blocks
-    AxisSums sums[UPHIP_MAX_PAGES];
+    AxisSums sums[UPHIP_MAX_POINTS];
     const EdgeArgs* edges = nullptr;
     MaskAssembleArgs assemble{};
+    // more than two points: every point's bands, one copy (k_mask_sums_points)
+    const PointBand* bands = nullptr;
+    int32_t band_cols = 0;  // the widest vertical band
   } mask_scan;
   struct {
     RotGeom geom{};
@@ -191,7 +194,7 @@ struct UphipBatch {
   int32_t* rot_lines = nullptr;  // scan-line point lists (k_rot_points)
   uph::Rect* pick_mask = nullptr;
   int32_t* pick_active = nullptr;
-  uph::RotateArgs* rot_args = nullptr; // [UPHIP_MAX_PAGES][cap]
+  uph::RotateArgs* rot_args = nullptr; // [max(points, UPHIP_MAX_PAGES)][cap]
   uint8_t* rot_scratch = nullptr;      // launch_rotate_mask's records (one launch at a time: stream-ordered)
   int32_t* rot_indep = nullptr;        // two-mask launch: mask 1 independent of deskew 0
   int32_t* rot_dep = nullptr;          // ... or redone after it
@@ -202,6 +205,12 @@ struct UphipBatch {
   int32_t* border_need = nullptr;      // cap: the chained border scan needs the middle rows
   uph::MaskArgs* border_mask_args = nullptr;
   int32_t* edge_res = nullptr;         // cap * npoints * 4
+  // more than two points (null otherwise): the options' points, uploaded once
+  // (k_ctl_points), and a rotation for every mask, cap * npoints
+  // (SheetCtl.rotation holds UPHIP_MAX_PAGES)
+  const UphipPoint* dpoints = nullptr;
+  float* rot_all = nullptr;
+  int32_t mask_scan_route = 0;         // more than two points: 0 one launch, 1 looped
   int32_t* border_res = nullptr;       // cap * nout * 4
   uint32_t* sums = nullptr;            // cap * sums_stride
   int64_t sums_stride = 0;

@@ -160,6 +160,9 @@ bool batch_plan(UphipBatch* b) {
   b->out_fmt = of;
   // layout defaults (sheet_stages.c:232-279) on the processing size
   const int32_t W = b->W, H = b->H;
+  if (o.point_count > UPHIP_MAX_POINTS)
+    return fail("batch: point_count %zu exceeds UPHIP_MAX_POINTS (%d)", (size_t)o.point_count,
+                UPHIP_MAX_POINTS);
   b->points.assign(o.points, o.points + o.point_count);
   int32_t mmw = o.mask_detection_parameters.maximum_width;
   int32_t mmh = o.mask_detection_parameters.maximum_height;
@@ -180,9 +183,6 @@ bool batch_plan(UphipBatch* b) {
   }
   if (mmw == -1) mmw = W;
   if (mmh == -1) mmh = H;
-  if (b->points.size() > UPHIP_MAX_PAGES)
-    return fail("batch: at most %d mask points are supported (got %zu)", UPHIP_MAX_PAGES,
-                b->points.size());
   b->mask_params = o.mask_detection_parameters;
   b->mask_params.maximum_width = mmw;
   b->mask_params.maximum_height = mmh;
@@ -287,7 +287,12 @@ bool batch_allocate(UphipBatch* b) {
   b->move_args = dalloc<MoveArgs>(b, (size_t)cap * UPHIP_MAX_PAGES);
   b->border_need = dalloc<int32_t>(b, cap);
   b->border_mask_args = dalloc<MaskArgs>(b, cap);
-  b->rot_args = dalloc<RotateArgs>(b, (size_t)cap * UPHIP_MAX_PAGES);
+  // a record per mask; more than two points: a rotation per mask as well
+  b->rot_args = dalloc<RotateArgs>(b, (size_t)cap * (np > 2 ? np : UPHIP_MAX_PAGES));
+  if (np > 2) {
+    b->rot_all = dalloc<float>(b, (size_t)cap * np);
+    if (!b->rot_all) return false;
+  }
   b->rot_scratch = dalloc<uint8_t>(b, rotate_scratch_bytes(b->max_w, b->max_h, cap));
   if (!b->rot_scratch) return false;
   b->rot_indep = dalloc<int32_t>(b, cap);
@@ -333,7 +338,8 @@ bool batch_allocate(UphipBatch* b) {
       b->dpow2 = dalloc<uint32_t>(b, imax(b->npow2, 1));
       UPH_HIP(hipMemcpy(b->dpow2, t, sizeof(uint32_t) * b->npow2, hipMemcpyHostToDevice));
     }
-    b->peaks = dalloc<int32_t>(b, (size_t)cap * UPHIP_MAX_PAGES * 4 * (na > 0 ? na : 1));
+    // k_rot_peaks and k_rot_select index it with RotGeom/RotSelectArgs.max_masks
+    b->peaks = dalloc<int32_t>(b, (size_t)cap * (np > 2 ? np : UPHIP_MAX_PAGES) * 4 * (na > 0 ? na : 1));
     int ms = o.deskew_parameters.deskewScanSize;
     if (ms == -1 || ms > 10000) ms = 10000;
     b->max_scan = imin(ms, imax(W, H));
@@ -363,6 +369,13 @@ struct Uploader {
   }
   template <class T>
   const T* all(const T& v) { return all(&v, 1); }
+  // a table the sheets share: one copy
+  template <class T>
+  const T* once(const T* v, size_t n) {
+    T* d = dalloc<T>(b, n);
+    ok = ok && d && (n == 0 || UPH_HIP(hipMemcpy(d, v, sizeof(T) * n, hipMemcpyHostToDevice)));
+    return d;
+  }
   // wipe_rectangle of an already clipped rectangle; an empty one has no block
   Fill fill(Rect clipped, UphipPixel c) {
     if (clipped.x1 < clipped.x0 || clipped.y1 < clipped.y0) return Fill{};
@@ -412,8 +425,12 @@ void prepare_mask_scan(UphipBatch* b, Uploader& up) {
   const UphipMaskDetectionParameters& p = b->mask_params;
   const int np = (int)b->points.size();
   const int32_t W = b->W, H = b->H;
-  EdgeArgs ea[UPHIP_MAX_PAGES * 4];
+  EdgeArgs ea[UPHIP_MAX_POINTS * 4];
   memset(ea, 0, sizeof(ea));
+  // more than two points: the bands of k_mask_sums_points, the regions below
+  std::vector<PointBand> bands;
+  if (np > 2)
+    for (int i = 0; i < 2 * np; i++) bands.push_back(PointBand{0, -1, i * imax(W, H)});
   for (int i = 0; i < np; i++) {
     const UphipPoint o = b->points[i];
     if (p.scan_direction.horizontal) {
@@ -421,6 +438,7 @@ void prepare_mask_scan(UphipBatch* b, Uploader& up) {
       const int32_t c0 = o.y - depth / 2, c1 = c0 + depth - 1;
       const Rect reg = clip(Rect{0, c0, W - 1, c1}, W, H);
       const int32_t off = (2 * i) * imax(W, H);
+      if (np > 2) bands[2 * i].lo = reg.y0, bands[2 * i].hi = reg.y1;
       if (reg.y1 >= reg.y0) b->args.mask_scan.sums[i].h = up.all(AxisArgs{reg, 0, 1});
       for (int k = 0; k < 2; k++)
         ea[i * 4 + k] = EdgeArgs{1, off, W, H, c0, c1, o.x - p.scan_size.width / 2,
@@ -432,6 +450,10 @@ void prepare_mask_scan(UphipBatch* b, Uploader& up) {
       const int32_t c0 = o.x - depth / 2, c1 = c0 + depth - 1;
       const Rect reg = clip(Rect{c0, 0, c1, H - 1}, W, H);
       const int32_t off = (2 * i + 1) * imax(W, H);
+      if (np > 2) {
+        bands[2 * i + 1].lo = reg.x0, bands[2 * i + 1].hi = reg.x1;
+        b->args.mask_scan.band_cols = imax(b->args.mask_scan.band_cols, reg.x1 - reg.x0 + 1);
+      }
       if (reg.x1 >= reg.x0) b->args.mask_scan.sums[i].v = up.all(AxisArgs{reg, 0, 1});
       for (int k = 2; k < 4; k++)
         ea[i * 4 + k] = EdgeArgs{1, off, H, W, c0, c1, o.y - p.scan_size.height / 2,
@@ -439,6 +461,7 @@ void prepare_mask_scan(UphipBatch* b, Uploader& up) {
                                  p.scan_threshold.vertical};
     }
   }
+  if (np > 2) b->args.mask_scan.bands = up.once(bands.data(), bands.size());
   b->args.mask_scan.edges = up.all(ea, (size_t)np * 4);
   b->args.mask_scan.assemble = MaskAssembleArgs{p, W, H, np, 1};
 }
@@ -501,10 +524,11 @@ void prepare_deskew(UphipBatch* b) {
     }
   rg.scan_size = dp.deskewScanSize;
   rg.scan_depth = dp.deskewScanDepth;
-  rg.max_masks = UPHIP_MAX_PAGES;
+  const int np = (int)b->points.size();  // the stride of b->peaks
+  rg.max_masks = np > 2 ? np : UPHIP_MAX_PAGES;
   ra.nangles = b->table.nangles;
   ra.nedges = rg.nedges;
-  ra.max_masks = UPHIP_MAX_PAGES;
+  ra.max_masks = np > 2 ? np : UPHIP_MAX_PAGES;
   ra.deviation_rad = dp.deskewScanDeviationRad;
 }
 
@@ -575,6 +599,8 @@ bool batch_prepare(UphipBatch* b) {
     A.post.border = up.border(o.border);
     A.post.post_border = up.border(o.post_border);
   }
+  // k_ctl_init carries two points; more go up here once (k_ctl_points)
+  if (b->points.size() > 2) b->dpoints = up.once(b->points.data(), b->points.size());
   if (!(dis & UPHIP_NO_MASK_SCAN)) prepare_mask_scan(b, up);
   if (!(dis & UPHIP_NO_DESKEW)) prepare_deskew(b);
   if (!(dis & UPHIP_NO_BORDER_SCAN) && !b->outside.empty()) prepare_border_scan(b, up);

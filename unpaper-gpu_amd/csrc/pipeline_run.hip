@@ -26,6 +26,18 @@ __global__ void k_ctl_init(SheetCtl* ctl, int count, int32_t npoints, UphipPoint
   for (int i = 0; i < UPHIP_MAX_PAGES; i++) c.rotation[i] = 0.0f;
 }
 
+// More than two points, after k_ctl_init: every point from the plan's copy
+// and a zero rotation for every mask (rot_all[s * npoints + i]).
+__global__ void k_ctl_points(SheetCtl* ctl, int count, int32_t npoints, const UphipPoint* points,
+                             float* rot_all) {
+  const int s = blockIdx.x;
+  if (s >= count) return;
+  for (int i = threadIdx.x; i < npoints; i += blockDim.x) {
+    ctl[s].points[i] = points[i];
+    rot_all[(int64_t)s * npoints + i] = 0.0f;
+  }
+}
+
 // Folds every sheet's status into the batch's sticky word at the end of a
 // run: k_ctl_init clears the per-sheet words at the start of the next run,
 // so without this a failure in an earlier of several runs enqueued before
@@ -186,11 +198,13 @@ __global__ void k_flip_rot2(SheetCtl* ctl, const RotateArgs* args, int64_t mstri
 // reduction keeps the largest peak and, among equal ones, the first angle --
 // the reference loop's `if (peak > max_peak)` from max_peak = 0 (an edge with
 // no positive peak keeps angle 0).
-__global__ void __launch_bounds__(64) k_rot_select(SheetCtl* ctl, const int32_t* peaks,
-                                                   const RotTable* table, const RotCombo* combo,
-                                                   RotSelectArgs a, RotateArgs* out, int count,
-                                                   const int32_t* only, const uint32_t* pow2,
-                                                   int npow2) {
+// rot_all (null in k_rot_select): a rotation for every mask, [s * a.max_masks + i]
+// (k_rot_select_all, more than two points).
+__device__ __forceinline__ void rot_select(SheetCtl* ctl, const int32_t* peaks,
+                                           const RotTable* table, const RotCombo* combo,
+                                           const RotSelectArgs& a, RotateArgs* out, int count,
+                                           const int32_t* only, const uint32_t* pow2, int npow2,
+                                           float* rot_all) {
   const int s = blockIdx.x, lane = threadIdx.x;
   if (s >= count) return;
   if (only && !only[s]) {
@@ -244,12 +258,29 @@ __global__ void __launch_bounds__(64) k_rot_select(SheetCtl* ctl, const int32_t*
     r.cosv = glibc::cosf(-r.result);
   }
   if (i < UPHIP_MAX_PAGES) c.rotation[i] = active ? r.result : 0.0f;
+  if (rot_all) rot_all[(int64_t)s * a.max_masks + i] = active ? r.result : 0.0f;
   RotateArgs ra;
   ra.mask = to_rect(c.masks[i]);
   ra.sinval = r.sinv;
   ra.cosval = r.cosv;
   ra.active = active && r.result != 0.0f;
   out[s] = ra;
+}
+
+__global__ void __launch_bounds__(64) k_rot_select(SheetCtl* ctl, const int32_t* peaks,
+                                                   const RotTable* table, const RotCombo* combo,
+                                                   RotSelectArgs a, RotateArgs* out, int count,
+                                                   const int32_t* only, const uint32_t* pow2,
+                                                   int npow2) {
+  rot_select(ctl, peaks, table, combo, a, out, count, only, pow2, npow2, nullptr);
+}
+
+__global__ void __launch_bounds__(64) k_rot_select_all(SheetCtl* ctl, const int32_t* peaks,
+                                                       const RotTable* table, const RotCombo* combo,
+                                                       RotSelectArgs a, RotateArgs* out, int count,
+                                                       const int32_t* only, const uint32_t* pow2,
+                                                       int npow2, float* rot_all) {
+  rot_select(ctl, peaks, table, combo, a, out, count, only, pow2, npow2, rot_all);
 }
 
 // center_mask (masks.c:222-249) for mask i -> MoveArgs
@@ -412,9 +443,12 @@ void detect_masks_all(UphipBatch* b, int count, bool sums_ready) {
   const int np = (int)b->points.size();
   const int32_t W = b->W, H = b->H;
   const PlaneRef R = cur_ref(planes_of(b, W, H), b->ctl);
-  if (!sums_ready)
+  const bool one_launch = np > 2 && b->mask_scan_route == 0;
+  if (one_launch)  // every entry the scans read is stored: nothing to clear
+    launch_mask_sums_points(R, A.bands, np, W, H, A.band_cols, b->sums, b->sums_stride, count, b->st);
+  if (!sums_ready && !one_launch)
     UPH_HIP(hipMemsetAsync(b->sums, 0, sizeof(uint32_t) * b->sums_stride * count, b->st));
-  for (int i = 0; i < np; i++) {
+  for (int i = 0; i < np && !one_launch; i++) {
     uint32_t* sums = b->sums + (2 * i) * imax(W, H);
     if (A.sums[i].h && !(sums_ready && i == 0))
       launch_axis_reduce(R, A.sums[i].h, 0, M_GRAY_SUM, W, H, sums, b->sums_stride, count, b->st);
@@ -560,9 +594,14 @@ bool deskew_all(UphipBatch* b, const Planes& P, int count) {
 #endif
     RotSelectArgs ra = b->args.deskew.select;
     ra.mask_index = i;
-    hipLaunchKernelGGL(k_rot_select, dim3(count), dim3(64), 0, b->st, b->ctl,
-                       b->peaks, b->dtable, b->dcombo, ra, b->rot_args + (int64_t)i * b->cap,
-                       count, only, b->dpow2, b->npow2);
+    if (b->points.size() > 2)  // a rotation kept for every mask
+      hipLaunchKernelGGL(k_rot_select_all, dim3(count), dim3(64), 0, b->st, b->ctl,
+                         b->peaks, b->dtable, b->dcombo, ra, b->rot_args + (int64_t)i * b->cap,
+                         count, only, b->dpow2, b->npow2, b->rot_all);
+    else
+      hipLaunchKernelGGL(k_rot_select, dim3(count), dim3(64), 0, b->st, b->ctl,
+                         b->peaks, b->dtable, b->dcombo, ra, b->rot_args + (int64_t)i * b->cap,
+                         count, only, b->dpow2, b->npow2);
   };
   // rotations are angles of the scan table, |angle| <= scan range
   auto rotate = [&](const RotateArgs* args, int nmask, const int32_t* indep,
@@ -625,6 +664,9 @@ bool run_batch(UphipBatch* b, int count, const uint8_t* src, int64_t spitch, int
   const UphipPoint p1 = b->points.size() > 1 ? b->points[1] : UphipPoint{0, 0};
   hipLaunchKernelGGL(k_ctl_init, dim3((count + 255) / 256), dim3(256), 0, b->st, b->ctl, count,
                      (int32_t)b->points.size(), p0, p1);
+  if (b->points.size() > 2)
+    hipLaunchKernelGGL(k_ctl_points, dim3(count), dim3(64), 0, b->st, b->ctl, count,
+                       (int32_t)b->points.size(), b->dpoints, b->rot_all);
   // ---- decode: pages -> working sheet (sheet_stages.c:44-185) ----------
   const int n = b->n_in;  // pages a sheet
   const Planes S0 = planes_of(b, b->sheet_w, b->sheet_h);

@@ -45,6 +45,20 @@ struct BorderEdgeArgs {
 void launch_axis_reduce(const PlaneRef& ref, const AxisArgs* args, int axis, int meas,
                         int32_t span_x, int32_t span_y, uint32_t* out, int64_t out_stride,
                         int count, hipStream_t st);
+// One point's band along one axis (detect_masks with more than two points):
+// the rows (axis 0) or columns (axis 1) its bars span, clipped to the image
+// (lo > hi: none), and where its W (or H) sums go in the sheet's sums row.
+struct PointBand {
+  int32_t lo, hi;
+  int32_t sums_offset;
+};
+// The M_GRAY_SUM column sums over band [2 i]'s rows and the row sums over band
+// [2 i + 1]'s columns of every point i, in one launch: every entry stored
+// (zeros for an empty band), no atomics, `out` need not be cleared.
+// band_cols: the widest axis-1 band.
+void launch_mask_sums_points(const PlaneRef& ref, const PointBand* bands, int npoints, int32_t W,
+                             int32_t H, int32_t band_cols, uint32_t* out, int64_t out_stride,
+                             int count, hipStream_t st);
 // Which kernel launch_axis_reduce takes (uphip_filter_arms reports it).
 enum AxisArm : int32_t {
   AXIS_COLSUM_GRAY,    // k_colsum_g

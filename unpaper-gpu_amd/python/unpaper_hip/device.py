@@ -81,7 +81,7 @@ EXPORTED = [
     "uphip_batch_tiff_sizes", "uphip_batch_tiff_download_async", "uphip_sink_tiff",
     "uphip_sink_tiff_multipage",
     "uphip_batch_set_page_size", "uphip_batch_decode_route", "uphip_source_max_geometry",
-    "uphip_batch_get_masks", "uphip_move_probe",
+    "uphip_batch_get_masks", "uphip_move_probe", "uphip_batch_set_mask_scan_route",
 ]
 
 
@@ -172,6 +172,7 @@ def load_library(path=LIB_PATH):
         "uphip_batch_get_report": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(A.SheetReport)]),
         "uphip_batch_get_masks": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(A.Rectangle),
                                               C.POINTER(C.c_float), C.c_int32]),
+        "uphip_batch_set_mask_scan_route": (C.c_int, [C.c_void_p, C.c_int32]),
         "uphip_batch_set_timing": (C.c_int, [C.c_void_p, C.c_int32]),
         "uphip_batch_kernel_times": (C.c_int, [C.c_void_p, C.POINTER(C.c_char_p),
                                                C.POINTER(C.c_float), C.c_int]),

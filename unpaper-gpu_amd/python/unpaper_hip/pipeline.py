@@ -278,6 +278,22 @@ class Batch:
         k = min(n, capacity)
         return n, [m[i] for i in range(k)], [r[i] for i in range(k)]
 
+    def set_mask_scan_route(self, route):
+        """How a batch of more than two mask-scan points sums its scan bars
+        from the next run on: 0 every point in one launch (the default), 1 per
+        point and axis, the looped twin (uphip_batch_set_mask_scan_route)."""
+        if self.lib.uphip_batch_set_mask_scan_route(self.handle, route) != 0:
+            _check(self.lib)
+            raise UnpaperHipError("batch_set_mask_scan_route failed")
+
+    def device_bytes(self):
+        """Device memory the batch holds (uphip_batch_device_bytes)."""
+        v = C.c_int64()
+        if self.lib.uphip_batch_device_bytes(self.handle, C.byref(v)) != 0:
+            _check(self.lib)
+            raise UnpaperHipError("batch_device_bytes failed")
+        return v.value
+
     def set_timing(self, enable=True):
         """Record per-stage HIP events on every run (uphip_batch_set_timing)."""
         self.lib.uphip_batch_set_timing(self.handle, 1 if enable else 0)
